@@ -9,7 +9,19 @@ step, clip + AdamW. Inputs are resident in HBM before the timed region. The froz
 runs on a second HIP stream beside step i's decoder (train._encoded); every timed batch is encoded exactly
 once inside the timed region (the first one without overlap).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line (the HIP events around the dominant
+  launch inside the timed steps cost no run of their own, so `roofline` stays). --full adds everything that takes
+  runs of its own: the CPU baseline (the oracle timed on the host cores; --no-cpu-baseline drops it again) and one
+  extra, untimed, probed step for `roofline_isolated` and the `decoder_attention` rows.
+  --dump-outputs DIR: after the timed steps rank 0 writes what a caller of the timed path holds after its last step
+  as DIR/<name>.npy (training: `avg_loss` = train_one_epoch's mean loss over the timed steps, float64, and `params` =
+  the trainable parameters after the last optimizer step, flattened in optimizer order, float32, a fixed seeded
+  sample of DUMP_MAX_ELEMS elements when there are more; C5: `tokens` = the last step's sampled token ids, float32).
+  Model init, batches, t draws and dropout seeds are all seeded, so the same arguments give the same inputs. The
+  bf16 step itself is not bit-reproducible (atomic accumulation orders): two runs of one build at C2, 5 + 20 steps,
+  agreed to 6e-7 relative in `avg_loss` and to 4.1e-3 absolute in `params` (AdamW moves a parameter whose gradient
+  is near zero by up to lr = 2e-4 per step in either direction, so 25 steps bound the spread by 5e-3).
   N>1: one rank per GPU over RCCL, per-GPU batch fixed ("weak"). Under torch.distributed.run (WORLD_SIZE set)
   the ranks come from the launcher; `python bench.py --gpus N` alone starts that launcher itself (a child
   process, before this process touches the GPU) and exits with its status. The world size the process group
@@ -55,7 +67,12 @@ def parse():
     ap.add_argument("--d-model", type=int, default=None)
     ap.add_argument("--heads", type=int, default=None)
     ap.add_argument("--precision", default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and the extra probed step "
+                         "(roofline_isolated, decoder_attention)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=4)
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--lfd-sync", action="store_true",
@@ -314,6 +331,32 @@ def param_checksums(models, world):
     return out
 
 
+DUMP_MAX_ELEMS = 8 * 1024 * 1024      # float32 elements per dumped array (32 MiB): every dump stays under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 kept). An array of more than DUMP_MAX_ELEMS
+    elements is written as a fixed sample of that many of its flattened elements (indices from a CPU generator with
+    seed 0, sorted), the same for every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        x = x.detach()
+        if x.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, x.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            x = x.reshape(-1)[idx.to(x.device)]
+        x = x.cpu().to(torch.float64 if x.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(path, name + ".npy"), x.numpy())
+
+
+def trainable_flat(models):
+    """The trainable parameters (decoder, speech projector, text embedding, text projector: the optimizer's order) as
+    one flat fp32 vector."""
+    enc, dec, sp, te, tp, sch = models
+    return torch.cat([p.detach().float().reshape(-1) for m in (dec, sp, te, tp) for p in m.parameters()])
+
+
 def cpu_baseline(args, models):
     """The CPU oracle (plain torch fp32 restatement of the reference step) timed on the host cores on a
     bounded sample: 2 utterances of the same geometry, `cpu_steps` steps (kind "port")."""
@@ -418,10 +461,12 @@ def run_c5(args, device, world, rank):
     ev[0].record()
     with rt.probing(["wavlm.conv1"]) as probes:
         for i in range(args.steps):
-            step(i)
+            tokens = step(i)
     ev[1].record()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, {"tokens": tokens})
     if world > 1:
         dist.barrier()
         tt = torch.tensor([el], device=device)
@@ -436,7 +481,7 @@ def run_c5(args, device, world, rank):
         achieved = kflops / (kms * 1e-3) / 1e12
         peak = BF16_PEAK_TFLOPS if args.precision == "bf16" else F32_PEAK_TFLOPS
         gpu_utt = gflop_per_utt(args)
-        cpu = None if (args.no_cpu_baseline or world > 1) else c5_cpu_baseline(args, models, smp)
+        cpu = c5_cpu_baseline(args, models, smp) if (args.full and not args.no_cpu_baseline and world == 1) else None
         out = {
             "metric": "jumpy-sampler inference utterances/sec (C5: 10 s @16 kHz, T_infer 20, r 5, exact, greedy, "
                       "seq_len 256)",
@@ -529,6 +574,9 @@ def main():
     tail_ev, T_.ALLREDUCE_TAIL = T_.ALLREDUCE_TAIL, None
     el = time.perf_counter() - t0
     rank_ms = [1000.0 * el / args.steps]
+    if args.dump_outputs and rank == 0:     # before anything below steps the optimizer again
+        dump_outputs(args.dump_outputs, {"avg_loss": torch.tensor([avg_loss], dtype=torch.float64),
+                                         "params": trainable_flat(models)})
     if world > 1:
         dist.barrier()
         tt = torch.zeros(world, device=device)
@@ -536,17 +584,19 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.SUM)      # every rank's own time (the line reports min / max)
         rank_ms = [1000.0 * float(x) / args.steps for x in tt.tolist()]
         el = max(float(x) for x in tt.tolist())
-    # decoder attention launches: HIP events on one extra, untimed step (an event pair around every attention
+    # --full: decoder attention launches: HIP events on one extra, untimed step (an event pair around every attention
     # launch inside the timed steps would add its own stream gaps to ms_per_step)
     # the same step with the encoder not overlapped (FDDM_NO_ENC_PIPELINE) also times the dominant launch alone
     # on the whole chip ("roofline_isolated"; inside the timed steps it shares the GPU with the decoder)
-    os.environ["FDDM_NO_ENC_PIPELINE"] = "1"
-    try:
-        with rt.probing(["wavlm.conv1", *ATTN_PROBES], replays=5) as aprobes:
-            T_.train_one_epoch(enc, dec, sp, te, tp, sch, loader_t[:1], opt, device, cfg, gs, None, 2, False)
-        torch.cuda.synchronize()
-    finally:
-        del os.environ["FDDM_NO_ENC_PIPELINE"]
+    aprobes = None
+    if args.full:
+        os.environ["FDDM_NO_ENC_PIPELINE"] = "1"
+        try:
+            with rt.probing(["wavlm.conv1", *ATTN_PROBES], replays=5) as aprobes:
+                T_.train_one_epoch(enc, dec, sp, te, tp, sch, loader_t[:1], opt, device, cfg, gs, None, 2, False)
+            torch.cuda.synchronize()
+        finally:
+            del os.environ["FDDM_NO_ENC_PIPELINE"]
     utt = args.batch * args.steps * world
     value = utt / el
     ms_step = 1000.0 * el / args.steps
@@ -561,13 +611,20 @@ def main():
         traffic, traffic_src = pmc_traffic(args)
         peak = BF16_PEAK_TFLOPS if args.precision == "bf16" else F32_PEAK_TFLOPS
         achieved = kflops / (kms * 1e-3) / 1e12
-        iev = aprobes["wavlm.conv1"]
-        iso_ms = sum(a.elapsed_time(b) for a, b in iev) / max(1, len(iev))
-        iso = kflops / (iso_ms * 1e-3) / 1e12
+        probed = {}
+        if aprobes is not None:     # --full: the extra step's figures
+            iev = aprobes["wavlm.conv1"]
+            iso_ms = sum(a.elapsed_time(b) for a, b in iev) / max(1, len(iev))
+            iso = kflops / (iso_ms * 1e-3) / 1e12
+            probed = {"roofline_isolated": {"kernel": "same launch, encoder not overlapped with the decoder, whole chip "
+                                                      "(untimed step)",
+                                            "achieved": round(iso, 1), "frac": round(iso / peak, 4),
+                                            "avg_ms": round(iso_ms, 4)},
+                      "decoder_attention": decoder_attention(args, aprobes, peak)}
         gpu_utt = gflop_per_utt(args)
         step_tflops = value / world * gpu_utt / 1e3
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(args, models)
         out = {
             "metric": "train-step utterances/sec (10 s @16 kHz, seq_len 256) at 1/2/4/8 MI355X",
@@ -586,9 +643,7 @@ def main():
                          # CUs (the decoder forward runs on the rest, train._encoded); frac_of_cus = achieved against
                          # that share of the chip's peak
                          "cus": conv_cus, "frac_of_cus": round(achieved / (peak * conv_cus / ncu), 4)},
-            "roofline_isolated": {"kernel": "same launch, encoder not overlapped with the decoder, whole chip (untimed step)",
-                                  "achieved": round(iso, 1), "frac": round(iso / peak, 4), "avg_ms": round(iso_ms, 4)},
-            "decoder_attention": decoder_attention(args, aprobes, peak),
+            **probed,
             "step_mfma_frac": round(step_tflops / peak, 4),
             "step_tflops": round(step_tflops, 1),
             "host_ms_per_step": round(1000.0 * host_s / args.steps, 3),
