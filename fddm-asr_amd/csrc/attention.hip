@@ -2598,6 +2598,7 @@ FDDM_API int fddm_attn_fwd(int dtype, const void* Q, long sq, const void* K, lon
                            long so, float* lse, const unsigned char* key_keep, const float* gate, const float* table,
                            int B, int H, int Lq, int Lk, float scale, float drop_p, unsigned long long seed,
                            unsigned long long stream, unsigned long long* drop_bits, int drop_bits_ready, void* hs) {
+  if (table && !gate) return (int)hipErrorInvalidValue;  // a bias table without its gate: no kernel takes that
   AttnArgs a{};
   a.dbits = (uint64_t*)drop_bits;
   a.bits_ready = drop_bits_ready;

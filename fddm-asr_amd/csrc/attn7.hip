@@ -1208,7 +1208,8 @@ int attn7_fwd(AttnArgs& a, hipStream_t s) {
   const int dm = a.thr16 == 0 ? 0 : 1;
   const int mk = a.key_keep != nullptr ? 2 : (a.Lk % 64) != 0 ? 1 : 0;
   const int ntiles = (a.Lk + 63) / 64;
-  const bool rel = a.table != nullptr;  // the caller checked a gate source (fddm_attn_fwd dispatch)
+  // the dispatcher's predicate (attention.hip run<T>): the REL build reads a gate, so a table alone is no bias
+  const bool rel = a.table != nullptr && (a.gate != nullptr || a.graw != nullptr || a.gx != nullptr);
   if (ntiles > 16 || (rel && dm)) return (int)hipErrorInvalidValue;  // LkP <= 1024; WavLM has no dropout
   const size_t lds = (size_t)4 * A7_TB + (dm ? 2048 : 0) + 16 + (size_t)ntiles * 64 * 4 +
                      (rel ? (size_t)2 * (ntiles * 64 + 160) * 4 : 0);

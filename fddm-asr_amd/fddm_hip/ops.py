@@ -321,6 +321,7 @@ def attn_fwd(q, k, v, out, lse, B, H, Lq, Lk, *, key_keep=None, gate=None, table
     _chk(q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1, "attention inputs need unit inner stride")
     _chk(q.dtype == k.dtype == v.dtype == out.dtype, "attention dtype mismatch")
     _chk(out.shape[1] % H == 0, "attention output width must be H * head_dim")
+    _chk(table is None or gate is not None, "a relative-position bias table needs its gate")
     dh = out.shape[1] // H
     _chk(1 <= dh <= 64, f"head_dim {dh} > 64 is not built")
     sc = 1.0 / math.sqrt(dh) if scale is None else scale

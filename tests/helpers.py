@@ -160,3 +160,79 @@ class CollectiveLog:
         for n, f in self._orig.items():
             setattr(dist, n, f)
         return False
+
+
+# ------------------------------------------------------------------ fwd8 (csrc/attn8.hip) guard inputs
+def fwd8_fast_path_rowsum(q, k, keep=None):
+    """What fwd8's fast path accumulates as one head's row sums, emulated on the CPU (csrc/attn8.hip: first_ref, the
+    chain-state comment and the guard before the fallback): q [Lq, 64], k [Lk, 64] already rounded to bf16, keep [Lk]
+    bool or None. Q' = bf16(q scale log2 e) at scale 1/8; scores Q' k^T in log2 units, masked keys -inf; the
+    reference is the bf16 rounding of the row's maximum over keys 0..31 (0 where that is -inf), fixed for the whole
+    row; the sum of exp2(score - reference) in float32. Returns (sum [Lq] float32, tripped [Lq] bool): tripped = the
+    guard's predicate, not (2^-40 <= sum <= 2^64), NaN included. It proves statements about test inputs (which rows
+    must take the fallback); it does not model the bf16 packing of P or the MFMA summation order and is no oracle for
+    the kernel's outputs."""
+    sl2 = torch.tensor(0.125, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32)
+    qp = (q.float() * sl2).to(torch.bfloat16)
+    s = (qp.double() @ k.double().t()).float()
+    if keep is not None:
+        s = s.masked_fill(~keep[None, :], float("-inf"))
+    m0 = s[:, :32].max(-1).values
+    rf = torch.where(torch.isinf(m0) & (m0 < 0), torch.zeros_like(m0), m0.to(torch.bfloat16).float())
+    tot = torch.exp2(s - rf[:, None]).sum(-1, dtype=torch.float32)
+    return tot, ~((tot >= 2.0 ** -40) & (tot <= 2.0 ** 64))
+
+
+# (kind, c, class, geometries) of fwd8_guard_inputs: what the fast path's row sum of a designated row does. The
+# constants hold for fwd8_guard_inputs' seed and these geometries (tests/test_cpu_attn_inputs.py asserts the margins); the
+# designated rows' sums spread over ~2^16 between rows and heads (the randn part of their scores), which is why the
+# inside constants sit further from the bounds than a single row would need.
+FWD8_GUARD_KINDS = [
+    ("rise", 12.0, "trips", "abcd"),   # the sum overflows float32: only the fallback can be right
+    ("rise", 4.7, "trips", "a"),       # above 2^64 but finite
+    ("rise", 3.3, "inside", "abcd"),   # the fast path at the top of its range
+    ("fall", 25.0, "trips", "abcd"),   # every exponential underflows, the sum is 0: only the fallback can be right
+    ("fall", 10.0, "trips", "a"),      # below 2^-40 but nonzero
+    ("fall", 6.8, "inside", "abcd"),   # the fast path at the bottom of its range
+]
+# name -> (B, H, Lq, Lk, dropout p, keys padded at the end of the last batch, designated query rows (None = all))
+FWD8_GUARD_GEOMS = {
+    "a": (1, 2, 256, 256, 0.1, 9, (37, 200)),
+    "b": (1, 2, 130, 200, 0.1, 0, (129,)),
+    "c": (1, 2, 600, 512, 0.0, 0, (5, 599)),
+    "d": (2, 3, 64, 96, 0.1, 0, None),
+}
+
+
+def fwd8_guard_inputs(geom, kind, c, seed=29):
+    """Inputs whose designated query rows drive fwd8's fixed-reference row sum to the edges of its guard (or past
+    them). Per head q, k, v ~ randn; one unit vector u shared by every head; the designated rows of q are
+    40 u + 0.05 randn, so their scaled score against a key shifted by s u is 5 s (7.2 s in log2 units) plus the randn
+    part. kind "rise": keys 0..31 get -c u and keys 32.. get +c u (the later keys exceed the first half-tile's
+    reference by ~14.4 c in log2 units); kind "fall": keys 0..31 are padding (the reference stays 0) and every key gets
+    -c u (every valid score sits ~7.2 c below it). Returns q [B, Lq, H*64], k, v [B, Lk, H*64] (float32), keep
+    [B, Lk] bool or None, and the designated rows as a list."""
+    B, H, Lq, Lk, _, tail, rows = FWD8_GUARD_GEOMS[geom]
+    gen = torch.Generator().manual_seed(seed)
+    u = torch.randn(64, generator=gen)
+    u = u / u.norm()
+    q, k, v = (torch.randn(B, L, H, 64, generator=gen) for L in (Lq, Lk, Lk))
+    rows = list(range(Lq)) if rows is None else list(rows)
+    q[:, rows] = 40.0 * u + 0.05 * torch.randn(B, len(rows), H, 64, generator=gen)
+    keep = None
+    if tail or kind == "fall":
+        keep = torch.ones(B, Lk, dtype=torch.bool)
+        if tail:
+            keep[B - 1, Lk - tail:] = False
+    if kind == "rise":
+        k[:, :32] -= c * u
+        k[:, 32:] += c * u
+    else:
+        keep[:, :32] = False
+        k -= c * u
+    return q.reshape(B, Lq, H * 64), k.reshape(B, Lk, H * 64), v.reshape(B, Lk, H * 64), keep, rows
+
+
+def fwd8_guard_cases():
+    """(geometry, kind, c, class) of every guard case: the representable-but-tripping constants on geometry a only."""
+    return [(g, kind, c, cls) for g in FWD8_GUARD_GEOMS for kind, c, cls, where in FWD8_GUARD_KINDS if g in where]

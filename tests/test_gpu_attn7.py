@@ -10,10 +10,12 @@ d=64 the LSE moves by up to ~2e-3, hence 4e-3 (the outputs stay within the bf16 
 Reference: models/denoise_decoder.py:129-130,164,169-176 (nn.MultiheadAttention, key_padding_mask, dropout on
 the probabilities).
 """
+import functools
+
 import pytest
 import torch
 
-from helpers import close
+from helpers import FWD8_GUARD_GEOMS, close, fwd8_fast_path_rowsum, fwd8_guard_cases, fwd8_guard_inputs
 from oracle import fddm_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -98,8 +100,24 @@ SHAPES = [  # (B, H, Lq, Lk, key-padding mask, dropout p)
 ]
 
 
-@pytest.mark.parametrize("B,H,Lq,Lk,masked,p", SHAPES)
-def test_attn7_forward_matches_float64(B, H, Lq, Lk, masked, p):
+FWD8_EXTRA = [  # forced fwd8 only
+    (2, 2, 600, 300, True, 0.1),     # three workgroups per (b, h), the last one partial
+    (1, 1, 32, 32, False, 0.1),      # exactly one half-tile: the pipeline-end row-sum MFMA carries the whole sum
+    (1, 2, 64, 33, False, 0.0),      # one key in the second half
+]
+
+
+def _families(shapes, extra8=()):
+    """Each shape under the default dispatch ("auto": fwd7 at these small B*H; it keeps the shape-only test id) and
+    with fwd8 forced (attn8.hip; not past Lk 1024, where the launch leaves the 32x32x16 family whatever is forced),
+    plus the fwd8-only shapes."""
+    name = lambda s: "-".join(str(x) for x in s)  # noqa: E731
+    return ([pytest.param("auto", *s, id=name(s)) for s in shapes] +
+            [pytest.param("fwd8", *s, id="fwd8-" + name(s)) for s in list(shapes) + list(extra8) if s[3] <= 1024])
+
+
+@pytest.mark.parametrize("family,B,H,Lq,Lk,masked,p", _families(SHAPES, FWD8_EXTRA))
+def test_attn7_forward_matches_float64(family, B, H, Lq, Lk, masked, p):
     D = H * 64
     gen = torch.Generator().manual_seed(Lq * 1000 + Lk)
     q, k, v = (torch.randn(B, L, D, generator=gen) for L in (Lq, Lk, Lk))
@@ -111,7 +129,7 @@ def test_attn7_forward_matches_float64(B, H, Lq, Lk, masked, p):
             keep[0, 3] = False
         if Lk > 130:
             keep[B - 1, 64:128] = False  # a whole 64-key tile of padding inside the range (skipped tile)
-    od, lse, _ = _run(B, H, Lq, Lk, keep, p, q, k, v)
+    od, lse, _ = _run(B, H, Lq, Lk, keep, p, q, k, v, family=family)
     ref, rlse = _ref(_heads(q, B, H), _heads(k, B, H), _heads(v, B, H), keep, p, 5, 9)
     close(od.float(), _back(ref), rtol=2e-2, what="attn7 out")
     # with few keys the LSE is close to one score, whose error is the bf16 rounding of Q' (|s| 2^-9), not averaged
@@ -119,10 +137,12 @@ def test_attn7_forward_matches_float64(B, H, Lq, Lk, masked, p):
     close(lse.view(B, H, Lq), rlse, rtol=0, atol=max(LSE_ATOL, 2.0 ** -8 * smax), what="attn7 lse")
 
 
-@pytest.mark.parametrize("B,H,Lq,Lk,masked,p", [SHAPES[0], SHAPES[1], SHAPES[4], SHAPES[6], SHAPES[9], SHAPES[10],
-                                                SHAPES[11], SHAPES[12]])
-def test_attn7_forward_then_backward_matches_float64(B, H, Lq, Lk, masked, p):
-    """The backward kernels read the forward's LSE and the same keep words: gradients vs float64 autograd."""
+@pytest.mark.parametrize("family,B,H,Lq,Lk,masked,p",
+                         _families([SHAPES[0], SHAPES[1], SHAPES[4], SHAPES[6], SHAPES[9], SHAPES[10], SHAPES[11],
+                                    SHAPES[12]], FWD8_EXTRA))
+def test_attn7_forward_then_backward_matches_float64(family, B, H, Lq, Lk, masked, p):
+    """The backward kernels read the forward's LSE and the same keep words: gradients vs float64 autograd. Under
+    "fwd8" the backward consumes fwd8's LSE and bf16 output, as the training step does."""
     D = H * 64
     gen = torch.Generator().manual_seed(7 + Lq + Lk)
     q, k, v, do = (torch.randn(B, L, D, generator=gen) for L in (Lq, Lk, Lk, Lq))
@@ -130,7 +150,7 @@ def test_attn7_forward_then_backward_matches_float64(B, H, Lq, Lk, masked, p):
     if masked:
         keep = torch.ones(B, Lk, dtype=torch.bool)
         keep[B - 1, max(1, Lk - 9):] = False
-    od, lse, (dq, dk, dv) = _run(B, H, Lq, Lk, keep, p, q, k, v, do)
+    od, lse, (dq, dk, dv) = _run(B, H, Lq, Lk, keep, p, q, k, v, do, family=family)
     qr, kr, vr = (_heads(x, B, H).requires_grad_(True) for x in (q, k, v))
     ref, _ = _ref(qr, kr, vr, keep, p, 5, 9)
     ref.backward(_heads(do, B, H))
@@ -172,14 +192,19 @@ def test_attn7_fused_backward_matches_float64_and_split_pair(B, H, Lq, Lk, maske
         close(a_.float(), b_.float(), rtol=2e-2, atol=1e-2, what=f"fused vs split {n}")
 
 
-@pytest.mark.parametrize("Lk", [256, 499])
-def test_attn7_rescale_path_with_growing_scores(Lk):
+@pytest.mark.parametrize("family,Lk", [pytest.param("auto", 256, id="256"), pytest.param("auto", 499, id="499"),
+                                       pytest.param("fwd8", 256, id="fwd8-256"),
+                                       pytest.param("fwd8", 499, id="fwd8-499")])
+def test_attn7_rescale_path_with_growing_scores(family, Lk):
     """Scores that grow along the keys (every 32-key half-tile exceeds the running maximum by far more than the
     2^8 rescale threshold) exercise the slow path on every half-tile; scores that fall along the keys keep the first
     half's reference. Forward against float64. The gradients at these scores (up to ~100, |K| up to ~25 per element)
     are bf16-limited in any kernel (dQ = scale sum_k dS K amplifies the bf16 rounding of P and dS by |K|): measured
     ~0.2-0.36 of max|dQ| for both families, so the backward is held to the round-4 family's error on the same inputs
-    (within 1.5x) instead of to float64."""
+    (within 1.5x) instead of to float64.
+    Under "fwd8" (fixed reference per chain, no rescale branch) the rising ramp ends ~2^130 above the first half-tile's
+    reference: the fast path's row sums overflow and every wave goes through the guard to the online-softmax fallback;
+    the falling ramp stays on the fast path (the first half-tile holds the maximum). Same checks, same bounds."""
     B, H, Lq = 2, 2, 128
     D = H * 64
     gen = torch.Generator().manual_seed(11)
@@ -197,29 +222,31 @@ def test_attn7_rescale_path_with_growing_scores(Lk):
         ref.backward(_heads(do, B, H))
         rg = [_back(x.grad) for x in (qr, kr, vr)]
         err = {}
-        for fam in ("auto", "v6"):
+        for fam in (family, "v6"):
             od, lse, grads = _run(B, H, Lq, Lk, None, 0.1, q, k, v, do, family=fam)
-            if fam == "auto":
+            if fam == family:
                 close(od.float(), _back(ref.detach()), rtol=2e-2, what=f"out (sign {sign})")
                 # the bf16 rounding of the pre-scaled Q moves scores by up to ~|s| 2^-9, as a bf16 rounding of the
                 # scores themselves would (torch's bf16 bmm): a tolerance relative to the LSE
                 close(lse.view(B, H, Lq), rlse.detach(), rtol=2.0 ** -9, atol=LSE_ATOL, what=f"lse (sign {sign})")
             err[fam] = [(g.float().cpu().double() - r).abs().max().item() / r.abs().max().item()
                         for g, r in zip(grads, rg)]
-        for n, a_, b_ in zip(("dq", "dk", "dv"), err["auto"], err["v6"]):
+        for n, a_, b_ in zip(("dq", "dk", "dv"), err[family], err["v6"]):
             assert a_ <= 1.5 * b_ + 2e-2, f"{n} (sign {sign}): attn7 rel err {a_:.3g} vs round-4 family {b_:.3g}"
 
 
-def test_attn7_fully_masked_rows_give_nan_like_softmax():
+@pytest.mark.parametrize("family", ["auto", "fwd8"])
+def test_attn7_fully_masked_rows_give_nan_like_softmax(family):
     """A batch whose keys are all padding: softmax over all -inf is NaN in the reference (torch), and so is every
-    output and LSE of that batch here; the other batch is unaffected."""
+    output and LSE of that batch here; the other batch is unaffected. In fwd8 such a batch entry still walks its
+    tiles (nact > 0) and ends with row sums of 0: the guard trips, the fallback's sums are 0 again -> NaN rows."""
     B, H, Lq, Lk = 2, 2, 96, 140
     D = H * 64
     gen = torch.Generator().manual_seed(3)
     q, k, v = (torch.randn(B, L, D, generator=gen) for L in (Lq, Lk, Lk))
     keep = torch.ones(B, Lk, dtype=torch.bool)
     keep[1] = False
-    od, lse, _ = _run(B, H, Lq, Lk, keep, 0.1, q, k, v)
+    od, lse, _ = _run(B, H, Lq, Lk, keep, 0.1, q, k, v, family=family)
     o = od.float().view(B, Lq, D)
     assert torch.isnan(o[1]).all() and torch.isnan(lse.view(B, H, Lq)[1]).all()
     ref, _ = _ref(_heads(q, B, H), _heads(k, B, H), _heads(v, B, H), keep, 0.1, 5, 9)
@@ -304,12 +331,15 @@ def test_decoder_long_audio_families_agree():
         close(res["auto"][1][n], res["v6"][1][n], rtol=6e-2, atol=1e-3, what=f"grad {n}")
 
 
-@pytest.mark.parametrize("p", [0.0, 0.1])
-def test_attn7_first_half_tile_masked_with_very_negative_scores(p):
+@pytest.mark.parametrize("family,p", [pytest.param("auto", 0.0, id="0.0"), pytest.param("auto", 0.1, id="0.1"),
+                                      pytest.param("fwd8", 0.0, id="fwd8-0.0"),
+                                      pytest.param("fwd8", 0.1, id="fwd8-0.1")])
+def test_attn7_first_half_tile_masked_with_very_negative_scores(family, p):
     """a query whose first 32 keys are all padding keeps m = -inf after its first half-tile; with every
     valid score far below the running reference (here ~ -130 in log2 units) the fast path's exponentials underflow
     to 0 and the row sum stays 0 unless the slow path runs while no finite reference exists. Output and LSE must be
-    finite and match float64 (torch's softmax is finite there)."""
+    finite and match float64 (torch's softmax is finite there). Under "fwd8" the chains' reference stays 0, every
+    exponential underflows, the row sums are 0 and the guard sends every wave to the fallback."""
     B, H, Lq, Lk = 1, 2, 64, 160
     D = H * 64
     gen = torch.Generator().manual_seed(13)
@@ -320,7 +350,7 @@ def test_attn7_first_half_tile_masked_with_very_negative_scores(p):
     v = torch.randn(B, Lk, D, generator=gen)
     keep = torch.ones(B, Lk, dtype=torch.bool)
     keep[:, :32] = False
-    od, lse, _ = _run(B, H, Lq, Lk, keep, p, q, k, v)
+    od, lse, _ = _run(B, H, Lq, Lk, keep, p, q, k, v, family=family)
     assert torch.isfinite(od.float()).all() and torch.isfinite(lse).all()
     ref, rlse = _ref(_heads(q, B, H), _heads(k, B, H), _heads(v, B, H), keep, p, 5, 9)
     close(od.float(), _back(ref), rtol=2e-2, what="out")
@@ -347,3 +377,108 @@ def test_fwd8_agrees_with_fwd7(B, H, Lq, Lk, masked, p):
     o7, l7, _ = _run(B, H, Lq, Lk, keep, p, q, k, v, family="fwd7")
     close(o8.float(), o7.float(), rtol=2e-2, what="fwd8 vs fwd7")
     close(l8, l7, rtol=0, atol=LSE_ATOL, what="lse fwd8 vs fwd7")
+
+
+@functools.lru_cache(maxsize=None)
+def _guard_case(geom, kind, c):
+    """One guard case's inputs, the emulated fast-path verdict per (b, h) and the float64 reference: built once,
+    shared by the families, never modified."""
+    B, H, Lq, Lk, p, _, _ = FWD8_GUARD_GEOMS[geom]
+    q, k, v, keep, rows = fwd8_guard_inputs(geom, kind, c)
+    qh, kh = (x.to(bf).view(B, -1, H, 64).transpose(1, 2) for x in (q, k))
+    trips = [[fwd8_fast_path_rowsum(qh[b, h], kh[b, h], None if keep is None else keep[b])[1].nonzero().flatten()
+              .tolist() for h in range(H)] for b in range(B)]
+    ref, rlse = _ref(_heads(q, B, H), _heads(k, B, H), _heads(v, B, H), keep, p, 5, 9)
+    return q, k, v, keep, rows, trips, ref, rlse
+
+
+@pytest.mark.parametrize("family", ["fwd8", "fwd7"])
+@pytest.mark.parametrize("geom,kind,c,cls", fwd8_guard_cases())
+def test_fwd8_guard_and_fallback_match_float64(geom, kind, c, cls, family):
+    """fwd8's guard on the final row sums and the online-softmax fallback behind it (attn8.hip, `redo`), forward
+    only, output and LSE of every row against float64 with the oracle's dropout mask. The inputs
+    (helpers.fwd8_guard_inputs) put designated query rows at, or past, the edges of what the fixed per-chain
+    reference can represent; the CPU emulation of the fast path's row sum proves first which rows trip the guard:
+    exactly the designated ones ("trips") or none ("inside": the fast path at the top / bottom of its range, 2^4
+    inside the bound by tests/test_cpu_attn_inputs.py). One tripped row sends its whole wave (64 queries, both
+    chains) through the fallback, so the other rows of those waves are recomputed there as well, while waves
+    without a designated row stay on the fast path in the same workgroup.
+    Proof that the fallback ran, for "rise" 12 and "fall" 25: the fast path's float32 sum of a designated row is
+    +inf, respectively exactly 0 (every exponential underflows), so its output would be 0 / NaN and its LSE inf /
+    NaN; a finite output and LSE matching float64 at those rows cannot have come from it.
+    Geometries and the template builds (DM = dropout, MK = key mask: 0 none, 1 ragged Lk, 2 mask bytes) they reach:
+    a: Lq 256 Lk 256 p 0.1, last 9 keys padded, rows 37 (wave 0, chain B) and 200 (wave 3, chain A): DM 1 MK 2,
+       waves 1 and 2 on the fast path; b: Lq 130 Lk 200 p 0.1, row 129 (wave 2, chain A; chain B lies past Lq, its
+       query group is clamped in the fallback's keep-dword read; ragged last key tile clamped in its staging): DM 1
+       MK 1 (rise) / MK 2 (fall); c: Lq 600 Lk 512 p 0, rows 5 and 599 (first and last workgroup, eight tiles): DM 0
+       MK 0 (rise) / MK 2 (fall); d: B 2 H 3 Lq 64 Lk 96 p 0.1, every row designated (no fast-path wave left): DM 1
+       MK 1 (rise) / MK 2 (fall).
+    fwd7 runs the same inputs as the control (its online softmax is the algorithm the fallback claims to be); it is
+    not an oracle. Tolerances are the file's: 2e-2 of the reference maximum, LSE rtol 2^-8 / LSE_ATOL (scores up to
+    ~130: the bf16 rounding of Q' moves them by ~|s| 2^-9)."""
+    B, H, Lq, Lk, p, _, _ = FWD8_GUARD_GEOMS[geom]
+    q, k, v, keep, rows, trips, ref, rlse = _guard_case(geom, kind, c)
+    want = sorted(rows) if cls == "trips" else []
+    assert all(t == want for tb in trips for t in tb), (want, trips)
+    assert torch.isfinite(ref).all() and torch.isfinite(rlse).all()
+    od, lse, _ = _run(B, H, Lq, Lk, keep, p, q, k, v, family=family)
+    assert torch.isfinite(od.float()).all() and torch.isfinite(lse).all()
+    close(od.float(), _back(ref), rtol=2e-2, what=f"{family} out")
+    close(lse.view(B, H, Lq), rlse, rtol=2.0 ** -8, atol=LSE_ATOL, what=f"{family} lse")
+
+
+def _per_head_close(od, lse, ref, rlse, B, H, Lq, what):
+    """Every (b, h) on its own: output within 2e-2 of that head's reference maximum, LSE within LSE_ATOL (a block
+    remap that swaps heads passes no per-tensor bound by luck of equal magnitudes, but fails these)."""
+    o = od.float().cpu().double().view(B, Lq, H, 64).transpose(1, 2)
+    ls = lse.cpu().double().view(B, H, Lq)
+    assert torch.isfinite(o).all() and torch.isfinite(ls).all(), f"{what}: non-finite values"
+    err, tol = (o - ref).abs().amax((-1, -2)), 2e-2 * ref.abs().amax((-1, -2))
+    bad = (err > tol).nonzero().tolist()
+    assert not bad, (f"{what}: out of tolerance at (b, h) {bad[:8]}: err {err.max().item():.3e}, "
+                     f"tol {tol.min().item():.3e}")
+    lerr = (ls - rlse).abs().amax(-1)
+    bad = (lerr > LSE_ATOL).nonzero().tolist()
+    assert not bad, f"{what}: lse out of tolerance at (b, h) {bad[:8]}: err {lerr.max().item():.3e}"
+
+
+def _grid_inputs(B, H, Lq, Lk, seed):
+    """randn k, v and 0.5 randn q, a key mask on the last batch. The half-scale queries keep the worst of ~65 000 rows
+    inside LSE_ATOL by the number formats alone: with 96 keys a row's LSE follows its few largest scores, and at unit
+    scale the bf16 rounding of Q' (shared by fwd7 and fwd8) moves the worst row's LSE by 3.7e-3 on the CPU, 4.5e-3
+    with a bf16 rounding of P before the row sum — no room under 4e-3 for any kernel; at half scale those figures are
+    0.7e-3 and 1.1e-3."""
+    gen = torch.Generator().manual_seed(seed)
+    q, k, v = (torch.randn(B, L, H * 64, generator=gen) for L in (Lq, Lk, Lk))
+    q = 0.5 * q
+    keep = torch.ones(B, Lk, dtype=torch.bool)
+    keep[B - 1, Lk - 9:] = False
+    return q, k, v, keep
+
+
+def test_auto_takes_fwd8_at_one_workgroup_per_cu():
+    """The benchmark-like grid: B * H = the device's CU count at Lq 256 (one fwd8 workgroup per (b, h) and CU; fwd7
+    would need two per CU), keep bits from the producer, a key mask on the last batch. The default dispatch must pick
+    fwd8 (bit-identical to the forced fwd8 run, not to the forced fwd7 run), and every (b, h) must match float64:
+    xcd_tile's block remap at a grid of that many blocks would show as whole heads swapped."""
+    nh = torch.cuda.get_device_properties(0).multi_processor_count
+    B, H = (nh // 8, 8) if nh % 8 == 0 else (nh, 1)
+    Lq, Lk, p = 256, 96, 0.1
+    q, k, v, keep = _grid_inputs(B, H, Lq, Lk, 77)
+    oa, la, _ = _run(B, H, Lq, Lk, keep, p, q, k, v, family="auto")
+    o8, l8, _ = _run(B, H, Lq, Lk, keep, p, q, k, v, family="fwd8")
+    o7, l7, _ = _run(B, H, Lq, Lk, keep, p, q, k, v, family="fwd7")
+    assert torch.equal(oa, o8) and torch.equal(la, l8), "auto is not fwd8 at one workgroup per CU"
+    assert not torch.equal(oa, o7), "auto is bit-identical to fwd7"
+    ref, rlse = _ref(_heads(q, B, H), _heads(k, B, H), _heads(v, B, H), keep, p, 5, 9)
+    _per_head_close(oa, la, ref, rlse, B, H, Lq, "auto")
+
+
+def test_fwd8_block_remap_remainder_grid():
+    """Seven blocks (B * H = 7, one workgroup each): xcd_tile's remainder branch r = n & 7 with q = n >> 3 = 0. Forced
+    fwd8 against float64, per head."""
+    B, H, Lq, Lk, p = 1, 7, 200, 96, 0.1
+    q, k, v, keep = _grid_inputs(B, H, Lq, Lk, 78)
+    od, lse, _ = _run(B, H, Lq, Lk, keep, p, q, k, v, family="fwd8")
+    ref, rlse = _ref(_heads(q, B, H), _heads(k, B, H), _heads(v, B, H), keep, p, 5, 9)
+    _per_head_close(od, lse, ref, rlse, B, H, Lq, "fwd8")

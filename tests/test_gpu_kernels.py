@@ -657,7 +657,7 @@ def test_attention_relgate_x_matches_gate_kernel_path(S):
                                           (70, "gx", False), (1000, "gate", False), (203, "gate", True)])
 def test_wavlm_attention_fwd7_bias_matches_fwd5_and_float64(S, src, masked):
     """Round 6: WavLM's gated relative-position attention on fwd7's bias build (csrc/attn7.hip REL: the bias slice in
-    four shifted LDS copies, the gate from a precomputed row / the projection's 8 extra columns / the attention input)
+    two shifted LDS copies, the gate from a precomputed row / the projection's 8 extra columns / the attention input)
     against the round-2 fwd5 (fddm_attn_set_kernels(5)) and float64 torch on the same bf16 inputs, for each gate
     source, a ragged key count (70, 203), two key passes past 512 (1000) and a key-padding mask."""
     o = ops()
