@@ -564,6 +564,11 @@ FDDM_API int fddm_ln_bwd(int dy_dtype, const float* dout, const float* s, const 
                          float* partials, void* hs) {
   if (N <= 0) return 0;
   if (d > 64 * LN_MAXPL) return (int)hipErrorInvalidValue;
+  // with FiLM, any parameter gradient makes ln_bwd_fused_kernel / ln_bwd_params_kernel add into both FiLM
+  // destinations; dgamma and dbeta are written as a pair
+  if (film_scale && (dgamma || dfilm_scale || dfilm_shift) && !(dfilm_scale && dfilm_shift))
+    return (int)hipErrorInvalidValue;
+  if ((dgamma == nullptr) != (dbeta == nullptr)) return (int)hipErrorInvalidValue;
   LnBwdArgs a{dout, s, mean, rstd, gamma, beta, film_scale, dres, dy_t, dgamma, dbeta, dfilm_scale, dfilm_shift,
               partials, N, d, rows_per_batch > 0 ? rows_per_batch : N, seed, stream, 0u, 1.f, g_seed_off};
   if (drop_p > 0.f) {

@@ -155,6 +155,8 @@ int fddm_ln_fwd(int x_dtype, int y_dtype, int out_dtype, const void* x, const vo
                 float* save_s, float* mean, float* rstd, long N, long d, long rows_per_batch, float eps, float drop_p,
                 unsigned long long seed, unsigned long long stream, const float* rope_cos, const float* rope_sin,
                 void* rope_out, long rope_L, void* hip_stream);
+/* dgamma and dbeta come as a pair; with film_scale, asking for any parameter gradient (dgamma or a dfilm_*) needs
+ * both dfilm_scale and dfilm_shift. Otherwise hipErrorInvalidValue, before anything is launched. */
 int fddm_ln_bwd(int dy_dtype, const float* dout, const float* s, const float* mean, const float* rstd,
                 const float* gamma, const float* beta, const float* film_scale, float* dres, void* dy_t,
                 float* dgamma, float* dbeta, float* dfilm_scale, float* dfilm_shift, long N, long d,
