@@ -852,11 +852,8 @@ FDDM_API int fddm_kl_fused(const float* logits, const long* xt, const long* x0, 
 #endif
   KLF_LAUNCH(8, 256)
   KLF_LAUNCH(16, 256)
-  KLF_LAUNCH(1, 512)
-  KLF_LAUNCH(4, 512)
-  KLF_LAUNCH(8, 512)
   KLF_LAUNCH(16, 512)
-  return (int)hipErrorInvalidValue;
+  return (int)hipErrorInvalidValue;  // V > 32768: no instantiation (fddm_hip.h, KL section)
 }
 
 // x[n] *= g[0] on the device, skipped (no memory traffic) when g[0] == 1

@@ -471,8 +471,9 @@ class KLFn(torch.autograd.Function):
             kl_tok, dz = ops.kl_fused(l2, xf, x0f, tc, betas, mask_u8, L, out_dtype=odt)
             loss, _ = ops.kl_reduce(kl_tok, mask_u8, B, L, want_w=False)
         else:
-            # vocabularies the one-pass kernel is not built for (V % 4 != 0, V > 32768, unaligned rows): the
-            # two-pass form — per-token KL, the masked-mean weights, then the weighted gradient
+            # rows the one-pass kernel is not built for (V % 4 != 0 or unaligned rows, up to V = 16384): the two-pass
+            # form — per-token KL, the masked-mean weights, then the weighted gradient. No kernel serves V > 32768
+            # (or V > 16384 on this path): ops.kl_fwd raises a ValueError there
             kl_tok = ops.kl_fwd(l2, xf, x0f, tc, betas, L)
             loss, w = ops.kl_reduce(kl_tok, mask_u8, B, L, want_w=True)
             one = torch.ones(1, device=l2.device, dtype=F32)

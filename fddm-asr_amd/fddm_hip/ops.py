@@ -494,8 +494,23 @@ def sample_q(x0, t, thr, K, seed, rng_stream=1):
     return xt
 
 
+# Vocabulary limits of the row kernels (one workgroup holds a whole row in registers; include/fddm_hip.h, KL section)
+KL_VEC_MAX_V = 32768        # fddm_kl_fwd/_bwd float4 kernels: V % 4 == 0 and 16-byte-aligned rows
+KL_SCALAR_MAX_V = 16384     # fddm_kl_fwd/_bwd scalar kernel (any V, any alignment): 256 threads x 64 elements
+KL_FUSED_MAX_V = 32768      # fddm_kl_fused (V % 4 == 0, aligned rows only): 512 threads x 16 float4 per row
+SOFTMAX_MAX_V = 16384       # fddm_softmax_rows/_bwd_rows: 256 threads x 64 elements
+
+
+def _chk_kl_vocab(name, V, *bufs):
+    vec = V % 4 == 0 and all(b is None or b.data_ptr() % 16 == 0 for b in bufs)
+    if V > (KL_VEC_MAX_V if vec else KL_SCALAR_MAX_V):
+        raise ValueError(f"{name}: V = {V} is outside the supported range V <= {KL_VEC_MAX_V} (V % 4 == 0 and "
+                         f"16-byte-aligned rows) or V <= {KL_SCALAR_MAX_V} (otherwise)")
+
+
 def kl_fwd(logits2d, xt, x0, t, betas, L):
     N, V = logits2d.shape
+    _chk_kl_vocab("kl_fwd", V, logits2d)
     kl = torch.empty(N, device=logits2d.device, dtype=torch.float32)
     call("fddm_kl_fwd", ptr(logits2d), ptr(xt), ptr(x0), ptr(t), ptr(betas), ptr(kl), N, L, V, stream())
     return kl
@@ -504,12 +519,10 @@ def kl_fwd(logits2d, xt, x0, t, betas, L):
 def kl_bwd(logits2d, xt, x0, t, betas, w, gscale, L, out_dtype=torch.float32):
     N, V = logits2d.shape
     dz = torch.empty(N, V, device=logits2d.device, dtype=out_dtype)
+    _chk_kl_vocab("kl_bwd", V, logits2d, dz)
     call("fddm_kl_bwd", ptr(logits2d), ptr(xt), ptr(x0), ptr(t), ptr(betas), ptr(w), ptr(gscale), ptr(dz),
          code(dz), N, L, V, stream())
     return dz
-
-
-KL_FUSED_MAX_V = 32768      # fddm_kl_fused: 512 threads x 16 float4 per row
 
 
 def kl_fused(logits2d, xt, x0, t, betas, mask_u8, L, out_dtype=torch.float32):
@@ -551,15 +564,22 @@ def axpy_if_bf16(x, y, g):
     return x
 
 
+def _chk_softmax_vocab(name, V):
+    if V > SOFTMAX_MAX_V:
+        raise ValueError(f"{name}: V = {V} is outside the supported range V <= {SOFTMAX_MAX_V}")
+
+
 def softmax_rows(x2d, out_dtype):
     N, V = x2d.shape
-    y = torch.empty(N, V, device=x2d.device, dtype=out_dtype)
+    _chk_softmax_vocab("softmax_rows", V)
+    y =torch.empty(N, V, device=x2d.device, dtype=out_dtype)
     call("fddm_softmax_rows", ptr(x2d), ptr(y), code(y), N, V, stream())
     return y
 
 
 def softmax_bwd_rows(y, dy, dz=None, accumulate=False):
     N, V = y.shape
+    _chk_softmax_vocab("softmax_bwd_rows", V)
     if dz is None:
         dz = torch.empty(N, V, device=y.device, dtype=torch.float32)
     call("fddm_softmax_bwd_rows", ptr(y), ptr(dy), ptr(dz), code(y), N, V, int(accumulate), stream())

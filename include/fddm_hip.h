@@ -190,7 +190,12 @@ int fddm_colsum(int dtype, const void* X, float* out, long M, long N, long ldx, 
 int fddm_cast(int src_dtype, int dst_dtype, const void* x, void* y, long n, void* hip_stream);
 
 /* ---- discrete diffusion: q_sample draw (train.py:180-188; diffusion_scheduler.py:31-50) and the
- *      categorical KL + exact gradient (train.py:190-255). thr: [T] uint32 keep thresholds. */
+ *      categorical KL + exact gradient (train.py:190-255). thr: [T] uint32 keep thresholds.
+ *      Vocabulary limits (one workgroup holds a row in registers; beyond them the call returns
+ *      hipErrorInvalidValue without a launch, and fddm_hip/ops.py raises a ValueError first):
+ *        fddm_kl_fwd / fddm_kl_bwd: V <= 32768 when V % 4 == 0 and logits and dz are 16-byte aligned, else V <= 16384;
+ *        fddm_kl_fused: V <= 32768, V % 4 == 0 and aligned rows only;
+ *        fddm_softmax_rows / fddm_softmax_bwd_rows: V <= 16384; fddm_softmax_bwd_add_bf16: V <= 32768, V % 8 == 0. */
 int fddm_sample_q(const long* x0, const long* t, const unsigned* thr, long* xt, long B, long L, long K,
                   unsigned long long seed, unsigned long long stream, void* hip_stream);
 int fddm_kl_fwd(const float* logits, const long* xt, const long* x0, const long* t, const float* betas, float* kl_tok,

@@ -127,6 +127,50 @@ def jumpy_case_inputs(i, B, L, K):
     return logits, xt
 
 
+def kl_term_ref64(logits, xt, x0, t, x_mask, betas, dtype=torch.float64):
+    """SchedulerAdapter.kl_term (train.py:190-255) per token and per element in float64: the formulas of
+    oracle.fddm_oracle.kl_term with every tensor (the fp32 logits and the fp32 betas) promoted first. Returns
+      kl_tok [B, L]     the per-token KL, masked tokens included,
+      dz     [B, L, V]  d loss / d logits = w xhat (g - sum_j g_j xhat_j), g = g0 + g1,
+      w      [B, L]     the masked-mean weights d loss / d kl_tok (mask / (count + eps) / B, or 1 / (L B)),
+      s      [B, L, V]  the per-element error scale w xhat_k (|g0_k| + |g1_k| + sum_j xhat_j (|g0_j| + |g1_j|)) with
+                        g0 = -Q M a_p / ((P + eps)(d_p + eps)) and g1 = [k = x_t] a_t S1 / (d_p + eps): the size of
+                        the terms whose rounding errors reach element k (|dz_k| itself is no usable scale where
+                        g_k is close to sum_j g_j xhat_j).
+    dtype=torch.float32 evaluates the same expressions in fp32 (what fp32 arithmetic costs per token, which the
+    oracle, returning only the loss, does not show); the reference is the float64 default."""
+    B, L, V = logits.shape
+    eps = 1e-8
+    K = float(V)
+    z = logits.to(dtype)
+    xhat = torch.softmax(z, dim=-1)
+    bt = betas[t - 1].to(dtype).view(B, 1)
+    bp = torch.where(t.eq(1), torch.zeros((), dtype=betas.dtype), betas[(t - 2).clamp(min=0)]).to(dtype).view(B, 1)
+    a_t, b_t = 1.0 - bt, bt / K
+    a_p, b_p = 1.0 - bp, bp / K
+    is_xt = torch.nn.functional.one_hot(xt, V).to(dtype)
+    is_x0 = torch.nn.functional.one_hot(x0, V).to(dtype)
+    M = b_t[..., None] + a_t[..., None] * is_xt
+    d_q = b_t + a_t * (x0 == xt).to(dtype)
+    d_p = b_t + a_t * torch.gather(xhat, -1, xt[..., None])[..., 0]
+    Q = M * (a_p[..., None] * is_x0 + b_p[..., None]) / (d_q[..., None] + eps)
+    P = M * (a_p[..., None] * xhat + b_p[..., None]) / (d_p[..., None] + eps)
+    kl_tok = (Q * (torch.log(Q + eps) - torch.log(P + eps))).sum(-1)
+    if x_mask is not None:
+        valid = x_mask.to(dtype)
+        w = valid / (valid.sum(1, keepdim=True) + eps) / B
+    else:
+        w = torch.full((B, L), 1.0 / (L * B), dtype=dtype)
+    S1 = (Q * P / (P + eps)).sum(-1)
+    g0 = -Q * M * a_p[..., None] / ((P + eps) * (d_p[..., None] + eps))
+    g1 = is_xt * (a_t * S1 / (d_p + eps))[..., None]
+    g = g0 + g1
+    dz = w[..., None] * xhat * (g - (g * xhat).sum(-1, keepdim=True))
+    ga = g0.abs() + g1.abs()
+    s = w[..., None] * xhat * (ga + (ga * xhat).sum(-1, keepdim=True))
+    return kl_tok, dz, w, s
+
+
 class CollectiveLog:
     """Records every torch.distributed collective issued inside the context (name, shape, dtype, reduce op), in
     issue order: DP ranks must issue the identical sequence (fddm_hip.dist, train.train_one_epoch)."""
