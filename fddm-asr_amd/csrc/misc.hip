@@ -219,11 +219,11 @@ __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ X, fl
 
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n) {
   const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i + 3 < n) {
+  if (i + 3 < n && (((uintptr_t)x) & 15) == 0) {  // 16-B load; x off a 16-B boundary takes the scalar loop
     const float4 v = *(const float4*)(x + i);
     y[i] = f2bf(v.x); y[i + 1] = f2bf(v.y); y[i + 2] = f2bf(v.z); y[i + 3] = f2bf(v.w);
   } else {
-    for (long j = i; j < n; ++j) y[j] = f2bf(x[j]);
+    for (long j = i; j < min(i + 4, n); ++j) y[j] = f2bf(x[j]);
   }
 }
 

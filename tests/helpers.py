@@ -171,6 +171,168 @@ def kl_term_ref64(logits, xt, x0, t, x_mask, betas, dtype=torch.float64):
     return kl_tok, dz, w, s
 
 
+# ------------------------------------------------------------------ fused AdamW (csrc/optim.hip) reference and inputs
+def _f32(x):
+    return float(np.float32(x))
+
+
+class AdamwScales:
+    """Per-element quantities of one adamw_step_ref step (float64): the update term u and the error scales."""
+    __slots__ = ("u", "s_m", "s_v", "s_u", "s_p", "coef")
+
+
+def adamw_step_ref(p, g, m, v, step, total_sq, *, lr, wd, b1, b2, eps, max_norm, grad_scale, dtype=torch.float64,
+                   torch_form=False):
+    """One fused clip + AdamW step (the order at the top of csrc/optim.hip) from a given state. `step` is the tensor's
+    step counter before the step (the bias corrections use t = step + 1), total_sq the sum of squares of the raw
+    gradients of the whole step. With s = grad_scale:
+        coef = s min(1, max_norm / (s sqrt(total_sq) + 1e-6))   (coef = s when max_norm is None or 0)
+        g' = coef g;  p1 = p (1 - lr wd);  m' = m + (1 - b1)(g' - m);  v' = b2 v + (1 - b2) g'^2
+        ss = lr / (1 - b1^t);  bc = sqrt(1 - b2^t);  u = ss m' / (sqrt(v') / bc + eps);  p' = p1 - u
+    Default form: the operation as the C ABI receives it — lr, lr wd, b1, b2, eps, max_norm, grad_scale (and the 1e-6
+    of the clip, a float literal in the kernel) are rounded to float32 first, everything after that is float64, the
+    bias corrections included. torch_form=True keeps the Python doubles (1 - b2 = 0.001 as in torch.optim.AdamW).
+    dtype=torch.float32 evaluates the same expressions in fp32 in the kernel's order (ss and bc in double, then
+    rounded, as the kernel does), without FMA contraction.
+    Returns p', m', v' (in dtype) and an AdamwScales of float64 tensors:
+        u    the update term
+        s_m  = |m| + |g'|
+        s_v  = v + g'^2
+        s_u  = ss (b1 |m| + (1 - b1) |g'|) / (sqrt(v') / bc + eps)   the cancellation-free size of u (|u| itself is no
+               usable scale where b1 m is close to -(1 - b1) g')
+        s_p  = |p| + |p'| + |u|"""
+    import math
+    if torch_form:
+        lr_, lrwd, b1_, b2_, eps_, tiny = float(lr), float(lr) * float(wd), float(b1), float(b2), float(eps), 1e-6
+        mn, s = float(max_norm or 0.0), float(grad_scale)
+    else:
+        lr_, lrwd, b1_, b2_, eps_, tiny = _f32(lr), _f32(float(lr) * float(wd)), _f32(b1), _f32(b2), _f32(eps), _f32(1e-6)
+        mn, s = _f32(max_norm or 0.0), _f32(grad_scale)
+    R = _f32 if dtype == torch.float32 else float       # the rounding of every scalar intermediate
+    coef = s
+    if mn > 0.0:
+        coef = R(s * min(1.0, R(mn / R(R(s * R(math.sqrt(float(total_sq)))) + tiny))))
+    t = float(step) + 1.0
+    ss = R(lr_ / (1.0 - b1_ ** t))
+    bc = R(math.sqrt(1.0 - b2_ ** t))
+    keep, omb1, omb2 = R(1.0 - lrwd), R(1.0 - b1_), R(1.0 - b2_)
+    P, G, M, V = (x.detach().to(dtype) for x in (p, g, m, v))
+    g1 = G * coef
+    p1 = P * keep
+    m1 = M + omb1 * (g1 - M)
+    v1 = V * b2_ + (omb2 * g1) * g1
+    den = v1.sqrt() / bc + eps_
+    u = ss * (m1 / den)
+    p2 = p1 - u
+    sc = AdamwScales()
+    Pd, Md, Vd, g1d, dend = P.double(), M.double(), V.double(), g1.double(), den.double()
+    sc.coef = coef
+    sc.u = u.double()
+    sc.s_m = Md.abs() + g1d.abs()
+    sc.s_v = Vd + g1d * g1d
+    sc.s_u = ss * (b1_ * Md.abs() + (1.0 - b1_) * g1d.abs()) / dend
+    sc.s_p = Pd.abs() + p2.double().abs() + sc.u.abs()
+    return p2, m1, v1, sc
+
+
+# fp32 evaluation of the step against float64, in units of 2^-24 x the scales, measured on the CPU over every scenario of
+# adamw_scenarios() on the tensors of adamw_tensors() (tests/test_cpu_optim_ref.py asserts them with 10 % headroom;
+# tests/test_gpu_optim.py allows the kernel ADAMW_C x these):
+#   |dp + du| <= E_P 2^-24 s_p (the decay and the final subtraction), |du| <= E_U 2^-24 s_u,
+#   |dm| <= E_M 2^-24 s_m, |dv| <= E_V 2^-24 s_v
+ADAMW_E = dict(P=1.19, U=6.17, M=1.03, V=1.98)
+ADAMW_C = 4.0              # the kernel differs from that evaluation only by FMA contraction
+ADAMW_HP = dict(lr=2e-4, wd=0.01, b1=0.9, b2=0.999, eps=1e-8)           # FusedAdamW's defaults
+ADAMW_HP2 = dict(lr=1e-3, wd=0.1, b1=0.8, b2=0.95, eps=1e-6)            # the second parameter group
+MT_CHUNK = 65536           # elements per block of the multi-tensor kernels (csrc/optim.hip)
+
+# (name, shape, parameter kind, gradient kind, unaligned, parameter group). Parameter kinds: unit = randn, small =
+# 1e-3 randn, zero. Gradient kinds: randn7 = randn with every 7th element exactly 0, logu = magnitudes log-uniform in
+# 1e-10 .. 1 with a random sign (reaches sqrt(v) / bc ~ eps). Every shape has a unit parameter and a logu gradient
+# somewhere in the set; 475 408 elements, 13 chunks.
+ADAMW_TENSORS = [
+    ("a", (257, 255), "unit", "logu", False, 0),    # one chunk, n % 4 = 3: vector loop + scalar tail (bf16: both copies)
+    ("b", (256, 256), "unit", "randn7", False, 0),  # exactly one chunk
+    ("c", (3, 43691), "unit", "logu", False, 1),    # three chunks, the last holds one element
+    ("d", (40963,), "unit", "randn7", False, 0),    # 1-D; n / 4 = 10240: one 8-deep sumsq pass + ragged single loads
+    ("e", (70,), "unit", "randn7", False, 1),
+    ("f", (1,), "unit", "logu", False, 0),
+    ("g", (65661,), "unit", "logu", True, 1),       # element offset 1 of a larger buffer: scalar paths, two chunks
+    ("h", (256, 256), "zero", "logu", False, 0),
+    ("i", (40963,), "small", "logu", False, 1),
+    ("j", (70,), "zero", "logu", False, 1),
+]
+
+
+def adamw_params(seed=11):
+    """{name: initial fp32 parameter} of ADAMW_TENSORS."""
+    gen = torch.Generator().manual_seed(seed)
+    out = {}
+    for name, shape, pk, _, _, _ in ADAMW_TENSORS:
+        x = torch.randn(*shape, generator=gen)
+        out[name] = x if pk == "unit" else 1e-3 * x if pk == "small" else torch.zeros(*shape)
+    return out
+
+
+def adamw_grads(k, mult=1.0, seed=23):
+    """{name: fp32 gradient} of draw k (one per step), scaled by mult."""
+    gen = torch.Generator().manual_seed(seed + 1000 * k)
+    out = {}
+    for name, shape, _, gk, _, _ in ADAMW_TENSORS:
+        x = torch.randn(*shape, generator=gen)
+        if gk == "randn7":
+            x.view(-1)[::7] = 0.0
+        else:
+            mag = torch.pow(10.0, -10.0 * torch.rand(*shape, generator=gen, dtype=torch.float64)).float()
+            x = torch.where(x < 0, -mag, mag)
+        out[name] = x * mult
+    return out
+
+
+def adamw_scenarios():
+    """name -> dict(mult = gradient multiplier, max_norm, grad_scale, groups = use both hyperparameter sets). Each runs
+    steps 1, 2, 3 and then one step with every step counter set to 999."""
+    return {
+        "clipped": dict(mult=10.0, max_norm=5.0, grad_scale=1.0, groups=False),
+        "not_clipped": dict(mult=1e-4, max_norm=5.0, grad_scale=1.0, groups=False),   # coef == grad_scale exactly
+        "no_clip": dict(mult=1.0, max_norm=None, grad_scale=1.0, groups=False),
+        "scaled_clipped": dict(mult=10.0, max_norm=5.0, grad_scale=0.125, groups=False),
+        "scaled_not_clipped": dict(mult=1e-4, max_norm=5.0, grad_scale=0.125, groups=False),
+        "groups": dict(mult=10.0, max_norm=5.0, grad_scale=1.0, groups=True),
+    }
+
+
+ADAMW_COUNTERS = (0.0, 1.0, 2.0, 999.0)     # the step counter before each of a scenario's four steps
+ADAMW_SKIP = {"b": 1, "i": 1}               # groups scenario: tensor -> index of the step at which its grad is None
+
+
+def adamw_scenario_grads(cfg, k):
+    """Gradients of step index k of a scenario (the groups scenario drops ADAMW_SKIP's tensors at their step)."""
+    G = adamw_grads(k, cfg["mult"])
+    if cfg["groups"]:
+        for n, ks in ADAMW_SKIP.items():
+            if ks == k:
+                del G[n]
+    return G
+
+
+def adamw_hp(name, groups):
+    """Hyperparameters of tensor `name`: the second set for group 1 of the groups scenario, else the defaults."""
+    grp = {n: gr for n, _, _, _, _, gr in ADAMW_TENSORS}[name]
+    return ADAMW_HP2 if groups and grp == 1 else ADAMW_HP
+
+
+def adamw_bounds(sc):
+    """The per-element bounds of tests/test_gpu_optim.py on |p - p_ref|, |m - m_ref|, |v - v_ref|."""
+    c = ADAMW_C * 2.0 ** -24
+    return (c * (ADAMW_E["P"] * sc.s_p + ADAMW_E["U"] * sc.s_u), c * ADAMW_E["M"] * sc.s_m, c * ADAMW_E["V"] * sc.s_v)
+
+
+def sumsq64(grads):
+    """Sum of squares of a {name: gradient} dict in float64."""
+    return sum(float((x.double() ** 2).sum()) for x in grads.values())
+
+
 class CollectiveLog:
     """Records every torch.distributed collective issued inside the context (name, shape, dtype, reduce op), in
     issue order: DP ranks must issue the identical sequence (fddm_hip.dist, train.train_one_epoch)."""
