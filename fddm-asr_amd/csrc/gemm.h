@@ -43,7 +43,9 @@ long gemm256_tiles(long M, long N);
 
 // 128x128 LDS-DMA ring GEMM (gemm128.hip) for outputs with too few 256x256 tiles. Layouts: A KC + B KC (STORE
 // bf16/f32, GELU, GELU_ONLY, DGELU, ACC_F32), A KC + B MC (STORE bf16/f32, DGELU, ACC_F32), A MC + B MC (ACC_F32, with
-// colsum). nz > 1: split-K slices of g.ksplit (ACC_F32 only, f32 atomics).
+// colsum). nz > 1: split-K slices of g.ksplit (ACC_F32 only, f32 atomics). ACC_F32 and ROPE_ACC take no bias:
+// gemm128_ok refuses ACC_F32 with g.bias set, and fddm_gemm sends such calls (and biased stores that would split) to
+// the register-staged kernel, which adds the bias on slice 0.
 bool gemm128_ok(const GemmArgs& g, bool akc, bool bkc, int epi, int out_dtype);
 int gemm128_launch(const GemmArgs& g, bool akc, bool bkc, int epi, int out_dtype, int nz, hipStream_t s);
 long gemm128_tiles(long M, long N);

@@ -697,16 +697,26 @@ FDDM_API int fddm_gemm_force_path(int path) {
   return old;
 }
 
+// Host-only record of the kernel family (and split-K slice count) the most recent GEMM entry point launched
+// (fddm_gemm_last_path): written by the dispatch below, read by tests. No device code, no effect on any launch.
+enum { LP_NONE = 0, LP_SMALL = 1, LP_BIG = 2, LP_256 = 3, LP_128 = 4, LP_GROUPED_SMALL = 5, LP_GROUPED_128 = 6 };
+static int g_last_path = LP_NONE;
+static void note_path(int family, int splits) { g_last_path = family | (splits << 8); }
+
+FDDM_API int fddm_gemm_last_path(void) { return g_last_path; }
+
 // dx[M][N] += rope_bwd(dy[M][K] @ w[K][N]) — the decoder's self-attention input gradient through RoPE in one launch
 // (gemm128 EPI_ROPE_ACC; replaces linear_dx into an f32 temporary + fddm_rope_bwd, ref models/denoise_decoder.py:
 // 150-156 apply_rope backward). bf16 dy / w, f32 dx and tables [L][N]; N % 128 == 0.
 FDDM_API int fddm_linear_dx_rope(const void* dy, long ldy, const void* w, long ldw, float* dx, long lddx, const float* cs,
                                  const float* sn, long M, long N, long K, long L, void* hip_stream) {
+  note_path(LP_NONE, 0);
   if (M <= 0 || N <= 0) return 0;
   if (!g128_enabled() || K % 8 || ldy % 8 || ldw % 8 || ((uintptr_t)dy & 15) || ((uintptr_t)w & 15) || ((uintptr_t)dx & 15))
     return (int)hipErrorInvalidValue;
   GemmArgs g{dy, ldy, 1L << 62, 0, w, ldw, dx, lddx, nullptr, nullptr, 1.f, M, N, K, 0, 0, 0u, 1.f, ConvGeo{1, 0, 0, 0}, 0, 0, 0, 0, K,
              nullptr, g_seed_off, cs, sn, L};
+  if (gemm128_ok(g, true, false, EPI_ROPE_ACC, FDDM_F32)) note_path(LP_128, 1);
   return gemm128_launch(g, true, false, EPI_ROPE_ACC, FDDM_F32, 1, (hipStream_t)hip_stream);
 }
 
@@ -714,6 +724,7 @@ FDDM_API int fddm_gemm(int dtype, int a_dtype, int a_kc, int b_kc, int epi, int 
                        long Mi, long sAb, const void* B, long ldb, void* C, long ldc, void* C2, const float* bias,
                        float alpha, long M, long N, long K, unsigned long long seed, unsigned long long stream,
                        float drop_p, float* colsum, void* hip_stream) {
+  note_path(LP_NONE, 0);
   if (M <= 0 || N <= 0) return 0;
   const int ech = dtype == FDDM_BF16 ? 8 : 4;
   // layout preconditions (16-B chunks never straddle a row end or the tile edge)
@@ -740,13 +751,18 @@ FDDM_API int fddm_gemm(int dtype, int a_dtype, int a_kc, int b_kc, int epi, int 
   hipStream_t s = (hipStream_t)hip_stream;
   // bf16 operands: the 256x256 kernel for outputs of >= half a round of its tiles (NT only), else the 128x128
   // LDS-DMA ring kernel (NT, NN with W as stored, TN weight gradients)
-  if (dtype == FDDM_BF16 && a_dtype == FDDM_BF16 && Mi >= M && g128_enabled() &&
+  // gemm128 splits K only for long reductions (a split slice adds its 128x128 tile with 64 KB of f32 atomics), and a
+  // split store becomes zero + accumulate. Its accumulate epilogue takes no bias, so a biased call that would
+  // accumulate there (EPI_ACC_F32, or a store that would split) runs on the register-staged kernel below, which adds
+  // the bias on slice 0.
+  const long t128 = gemm128_tiles(M, N);
+  const bool split128 = out_dtype == FDDM_F32 && (epi == EPI_STORE || epi == EPI_ACC_F32) && t128 < 192 && K >= 4096;
+  const bool bias_acc128 = bias && (epi == EPI_ACC_F32 || split128);
+  if (dtype == FDDM_BF16 && a_dtype == FDDM_BF16 && Mi >= M && g128_enabled() && !bias_acc128 &&
       !(a_kc && b_kc && !colsum && g256_enabled() && gemm256_ok(g, epi, out_dtype, false) && prefer_256(M, N)) &&
       gemm128_ok(g, a_kc, b_kc, epi, out_dtype) && (!colsum || !a_kc)) {
     int nz128 = 1;
-    const long t128 = gemm128_tiles(M, N);
-    // split-K only for long reductions: a split slice adds its 128x128 tile with 64 KB of f32 atomics
-    if (out_dtype == FDDM_F32 && (epi == EPI_STORE || epi == EPI_ACC_F32) && t128 < 192 && K >= 4096) {
+    if (split128) {
       long want = (256 + t128 - 1) / t128;
       nz128 = (int)std::max(1L, std::min(want, K / 2048));
       if (nz128 > 1) {
@@ -760,6 +776,7 @@ FDDM_API int fddm_gemm(int dtype, int a_dtype, int a_kc, int b_kc, int epi, int 
         }
       }
     }
+    note_path(LP_128, nz128);
     return gemm128_launch(g, a_kc, b_kc, epi, out_dtype, nz128, s);
   }
   // split-K when the output has too few 128x128 tiles to fill 256 CUs (weight gradients, small N):
@@ -786,14 +803,19 @@ FDDM_API int fddm_gemm(int dtype, int a_dtype, int a_kc, int b_kc, int epi, int 
     }
   }
   if (dtype == FDDM_BF16 && a_dtype == FDDM_BF16 && a_kc && b_kc && nz == 1 && Mi >= M && !colsum &&
-      g256_enabled() && gemm256_ok(g, epi, out_dtype, false) && prefer_256(M, N))
+      g256_enabled() && gemm256_ok(g, epi, out_dtype, false) && prefer_256(M, N)) {
+    note_path(LP_256, 1);
     return gemm256_launch(g, epi, out_dtype, false, s);
+  }
   if (dtype == FDDM_BF16 && a_dtype == FDDM_BF16 && a_kc && b_kc && nz == 1 && Mi >= M && !colsum &&
-      out_dtype == FDDM_BF16 && big_ok(g, false) && big_enabled()) {
+      out_dtype == FDDM_BF16 && big_ok(g, false) && big_enabled() &&
+      (epi == EPI_STORE || epi == EPI_GELU || epi == EPI_GELU_ONLY)) {
+    note_path(LP_BIG, 1);
     if (epi == EPI_STORE) return launch_big<EPI_STORE, bf16_t, false>(g, s);
     if (epi == EPI_GELU) return launch_big<EPI_GELU, bf16_t, false>(g, s);
     if (epi == EPI_GELU_ONLY) return launch_big<EPI_GELU_ONLY, bf16_t, false>(g, s);
   }
+  note_path(LP_SMALL, nz);
   if (dtype == FDDM_BF16) {
     if (a_dtype == FDDM_BF16) return dispatch_layout<bf16_t, bf16_t>(a_kc, b_kc, epi, out_dtype, g, s, nz);
     if (a_dtype == FDDM_F32) return dispatch_layout<bf16_t, float>(a_kc, b_kc, epi, out_dtype, g, s, nz);
@@ -812,6 +834,7 @@ FDDM_API int fddm_conv1d_gemm(int dtype, int epi, const void* x, long lda, long 
                               long cpad, const void* W, void* out, long ldc, const float* bias, long Bn, long Tout,
                               long N, long K, int groups, void* hip_stream) {
   const int ech = dtype == FDDM_BF16 ? 8 : 4;
+  note_path(LP_NONE, 0);
   if (Bn <= 0 || Tout <= 0) return 0;
   if (K % ech || Cg % ech || lda % ech || sAb % ech || ((uintptr_t)x & 15) || ((uintptr_t)W & 15))
     return (int)hipErrorInvalidValue;
@@ -819,12 +842,16 @@ FDDM_API int fddm_conv1d_gemm(int dtype, int epi, const void* x, long lda, long 
              ConvGeo{Cg, cstride, cpad, Tin}, Cg, N * K, N, N, K, nullptr};
   hipStream_t s = (hipStream_t)hip_stream;
   if (dtype == FDDM_BF16 && groups == 1 && g256_enabled() && gemm256_ok(g, epi, FDDM_BF16, true) &&
-      prefer_256(g.M, N))
+      prefer_256(g.M, N)) {
+    note_path(LP_256, 1);
     return gemm256_launch(g, epi, FDDM_BF16, true, s);
+  }
   if (dtype == FDDM_BF16 && groups == 1 && big_ok(g, true) && big_enabled()) {
+    note_path(LP_BIG, 1);
     if (epi == EPI_GELU_ONLY) return launch_big<EPI_GELU_ONLY, bf16_t, true>(g, s);
     return launch_big<EPI_STORE, bf16_t, true>(g, s);
   }
+  note_path(LP_SMALL, 1);
   if (dtype == FDDM_BF16) {
     if (epi == EPI_GELU_ONLY) return launch<bf16_t, bf16_t, true, true, EPI_GELU_ONLY, bf16_t, true>(g, s, groups);
     return launch<bf16_t, bf16_t, true, true, EPI_STORE, bf16_t, true>(g, s, groups);
@@ -911,6 +938,7 @@ static int g128_ncu() {
 FDDM_API int fddm_gemm_dw_grouped(int n, const void* const* dy, const long* ldy, const void* const* x, const long* ldx,
                                   float* const* dw, const long* lddw, float* const* db, const long* M, const long* N,
                                   const long* K, long kchunk, void* hip_stream) {
+  note_path(LP_NONE, 0);
   if (n <= 0) return 0;
   if (n > GROUP_MAX || n > G128_GROUP_MAX) return (int)hipErrorInvalidValue;
   bool g128 = g128_enabled() && kchunk <= 0;
@@ -946,6 +974,7 @@ FDDM_API int fddm_gemm_dw_grouped(int n, const void* const* dy, const long* ldy,
       total += ga.tn[i] * ga.tm[i] * ga.nz[i];
     }
     ga.start[n] = total;
+    note_path(LP_GROUPED_128, *std::max_element(ga.nz, ga.nz + n));
     return gemm128_grouped_dw(ga, total, (hipStream_t)hip_stream);
   }
   if (kchunk <= 0) kchunk = 8192;
@@ -974,6 +1003,7 @@ FDDM_API int fddm_gemm_dw_grouped(int n, const void* const* dy, const long* ldy,
     total += ga.tn[p] * ga.tm[p] * (int)nz;
   }
   ga.start[n] = total;
+  note_path(LP_GROUPED_SMALL, *std::max_element(ga.nz, ga.nz + n));
   hipLaunchKernelGGL((gemm_grouped_kernel<bf16_t, bf16_t, false, false, EPI_ACC_F32, float>), dim3(total), dim3(256),
                      4 * GTILE_BYTES, (hipStream_t)hip_stream, ga);
   return (int)hipGetLastError();

@@ -465,6 +465,9 @@ bool gemm128_ok(const GemmArgs& g, bool akc, bool bkc, int epi, int out_dtype) {
   if (aext * 2 >= (1L << 31) || bext * 2 >= (1L << 31)) return false;
   if (((g.M - 1) * g.ldc + g.N) * 4 >= (1L << 31)) return false;
   if (!akc && bkc) return false;
+  // the f32-accumulate epilogue (and with it every split-K slice) never reads g.bias: such calls belong to the
+  // register-staged kernel, which adds the bias on slice 0
+  if (epi == EPI_ACC_F32 && g.bias) return false;
   if (epi == EPI_ROPE_ACC)  // whole 128-column tiles of partner pairs, tables and output 16-B aligned
     return akc && !bkc && out_dtype == FDDM_F32 && g.N % 128 == 0 && g.ldc % 4 == 0 && g.rL > 0 && g.rcs && g.rsn &&
            !(((uintptr_t)g.rcs | (uintptr_t)g.rsn) & 15);

@@ -105,6 +105,19 @@ def gemm_force_path(name: str) -> str:
     return {v: k for k, v in GEMM_PATHS.items()}[old]
 
 
+GEMM_FAMILIES = ("none", "small", "big", "256", "128", "grouped-small", "grouped-128")
+
+
+def gemm_last_path():
+    """(family, split-K slices) of the kernel the most recent gemm / conv1d_gemm / linear_dw_grouped / linear_dx_rope
+    call launched (fddm_gemm_last_path): family is one of GEMM_FAMILIES, "none" when the call launched nothing. A
+    host-side record for tests, which must know the kernel they measured: gemm_force_path only enables a family, and a
+    shape outside its preconditions falls through to the register-staged kernel."""
+    from ._lib import lib
+    v = lib().fddm_gemm_last_path()
+    return GEMM_FAMILIES[v & 0xFF], v >> 8
+
+
 ATTN_KERNELS = {"auto": 0, "v6": 1, "nofused": 2, "fwd7": 3, "fwd8": 4, "relfwd5": 5}
 
 
@@ -123,6 +136,10 @@ def attn_force_kernels(name: str) -> str:
 def gemm(A, B, C, M, N, K, *, a_kc=True, b_kc=True, lda, ldb, ldc, epi=EPI_STORE, bias=None, alpha=1.0,
          C2=None, Mi=0, sAb=0, drop_p=0.0, seed=0, rng_stream=0, colsum=None):
     """C[m][n] = alpha * sum_k A(m,k) B(n,k) (+bias, epilogue). Compute dtype = B.dtype.
+    bias (f32 [N]) is added once whatever kernel runs: epi=EPI_ACC gives C += alpha A B^T + bias, and an f32 store or
+    accumulate that the library splits along K adds it on the first slice only (such biased calls run on the
+    register-staged kernel, never on the 128x128 LDS-DMA ring). alpha != 1 is supported by every family but the
+    persistent 256x256 kernel, which such calls never reach.
     Operands that miss the kernels' layout preconditions (a dimension or leading dimension not a multiple of 8, e.g.
     a ragged vocabulary) run zero-padded copies (_gemm_padded) — unbatched calls only: a batched / strided call
     (Mi or sAb set) with such operands raises."""

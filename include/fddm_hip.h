@@ -33,6 +33,10 @@ const char* fddm_error_string(int code);
  *      colsum (optional, M/N-contiguous A only): colsum[m] = sum_k A(m,k) — the fused bias gradient of
  *      a weight-gradient GEMM dW = dY^T X (colsum = sum over tokens of dY); like C it is overwritten
  *      for EPI_STORE and accumulated (+=) for EPI_ACC.
+ *      bias is added exactly once in every form, split-K (f32 store / accumulate of a long reduction, where the
+ *      slices combine with f32 atomics) and accumulate included: C += alpha A B^T + bias for EPI_ACC. Biased calls
+ *      that accumulate or split run on the register-staged 128x128 kernel (the LDS-DMA ring's accumulate epilogue
+ *      takes no bias); alpha != 1 never runs on the 256x256 kernel.
  *      Replaces every nn.Linear / F.linear forward and backward on the path:
  *      models/denoise_decoder.py:98-100,129-145,229,238  models/projection.py:14-55
  *      models/acoustic_encoder.py:55  HF modeling_wavlm.py:93-105,125-128,274-295 */
@@ -243,6 +247,13 @@ int fddm_lfd_std_bwd_apply(int zt_dtype, const float* dzt, const void* zt, const
  *      128x128 only, 3 256x256 wherever its preconditions hold, 4 128x128 LDS-DMA ring wherever they hold). Returns
  *      the previous setting. Process-wide; the train step never sets it. */
 int fddm_gemm_force_path(int path);
+/* ---- which kernel the most recent fddm_gemm / fddm_conv1d_gemm / fddm_gemm_dw_grouped / fddm_linear_dx_rope call
+ *      launched (a host-side record for tests; no device code, no effect on any launch): bits 0-7 the family — 0 none
+ *      (nothing to launch, or rejected before a kernel was chosen), 1 register-staged 128x128, 2 256x128 "big",
+ *      3 persistent 256x256, 4 128x128 LDS-DMA ring, 5 grouped register-staged, 6 grouped LDS-DMA ring — and bits 8..
+ *      the number of split-K slices (grouped launches: the largest of their problems'). Meaningful when the call
+ *      returned 0. Process-wide, not thread-safe. */
+int fddm_gemm_last_path(void);
 /* ---- attention kernel-family override for tests and diagnostics: 1 = the 16x16x32-MFMA kernels (fwd6, dq4 / dkv4,
  *      bwd3s) wherever the 32x32x16-MFMA family (csrc/attn7.hip) would run, 2 = the 32x32x16 family without its fused
  *      backward (dq7 + dkv7 at every Lk), 3 = the default with every forward on the one-chain fwd7, 4 = the default

@@ -442,3 +442,383 @@ def fwd8_guard_inputs(geom, kind, c, seed=29):
 def fwd8_guard_cases():
     """(geometry, kind, c, class) of every guard case: the representable-but-tripping constants on geometry a only."""
     return [(g, kind, c, cls) for g in FWD8_GUARD_GEOMS for kind, c, cls, where in FWD8_GUARD_KINDS if g in where]
+
+
+# ------------------------------------------------------------------ GEMM families (csrc/gemm.hip, gemm128.hip, gemm256.hip)
+# Reference, per-element bounds, inputs and the case table shared by tests/test_cpu_gemm_ref.py (which sets the
+# constants below from the reference alone) and tests/test_gpu_gemm.py (which runs the kernels).
+U24 = 2.0 ** -24
+EPI_STORE, EPI_GELU, EPI_ACC, EPI_GELU_ONLY, EPI_DGELU = 0, 1, 2, 3, 4
+EPI_NAMES = {EPI_STORE: "store", EPI_GELU: "gelu+c2", EPI_ACC: "acc", EPI_GELU_ONLY: "gelu", EPI_DGELU: "dgelu"}
+GEMM_ALPHAS = (1.0, -0.375, 1.0 / 1536.0)
+GEMM_GELU_ABS = 2e-6           # gelu_f against the erf GELU (test_gelu_fast_erf_accuracy's bar)
+GEMM_GELU_BF16OUT_ABS = 2.6e-5  # gelu_bf16out, the 256x256 kernel's GELU-only epilogue (csrc/common.h)
+GEMM_DGELU_REL = 2e-6          # gelu_grad: |err| <= 2e-6 |y| (common.h documents 1e-7 for Phi)
+# fp32 evaluation (64-wide K tiles added in order, split-K slices added in order, then alpha, bias, c_old) against
+# float64 in units of 2^-24 s, the maximum over every case of gemm_cases() (3.43, 2.82) and of CONV_CASES as im2col
+# GEMMs (6.66, 5.34) per compute dtype (f32, bf16), measured on the CPU
+# (tests/test_cpu_gemm_ref.py asserts them; the constants keep 10 % headroom). The kernels are allowed GEMM_C = 8 E units:
+# the margin covers the MFMA-internal summation order, gemm128's k-half split, the order of the split-K atomics and the
+# epilogue's roundings. Hard cap 64.
+GEMM_E = {"f32": 3.8, "bf16": 3.1, "conv-f32": 7.3, "conv-bf16": 5.9}
+GEMM_C = {k: 8.0 * v for k, v in GEMM_E.items()}
+
+
+class GemmRef:
+    __slots__ = ("y", "s", "act", "lin", "add", "scale", "epi", "colsum", "colsum_s")
+
+
+def gelu_grad64(x):
+    return 0.5 * (1.0 + torch.erf(x * 0.7071067811865476)) + x * torch.exp(-0.5 * x * x) * 0.3989422804014327
+
+
+def gemm_ref64(A, B, *, bias=None, alpha=1.0, c_old=None, epi=EPI_STORE, pre=None, keep=None, drop_p=0.0, prod=None):
+    """Float64 reference of one fddm_gemm call. A [M, K], B [N, K]: the logical operands, already rounded to the
+    compute dtype and promoted to float64 (any device). alpha as the C ABI receives it (a float32 value).
+      y        alpha A B^T + bias (+ c_old)
+      s        |alpha| (|A| |B|^T) + |bias| + |c_old|: the size of the terms whose roundings reach each element
+      act      the epilogue's second value: gelu(y) (EPI_GELU, EPI_GELU_ONLY) or y (Phi(pre) + pre phi(pre)) (EPI_DGELU),
+               times the dropout mask keep / (1 - p) when keep (bool [M, N], oracle dropout_keep) is given; else None
+      lin      |d act / d y| without the dropout factor: |gelu'(y)| or |gelu'(pre)|
+      add      the absolute slack of act that scales with the data: 2e-6 |y| for EPI_DGELU, else 0
+      scale    keep / (1 - p) (1 without dropout): dropped elements get bound 0, i.e. must be exactly 0
+      colsum   A.sum(K) and colsum_s = |A|.sum(K), the fused bias gradient of an M/N-contiguous A
+    prod = (A B^T, |A| |B|^T) computed earlier from the same operands (cases that share a shape share the products)."""
+    r = GemmRef()
+    a = float(alpha)
+    P, S = prod if prod is not None else (A @ B.t(), A.abs() @ B.abs().t())
+    r.y = a * P
+    r.s = abs(a) * S
+    if bias is not None:
+        r.y = r.y + bias.double()[None, :]
+        r.s = r.s + bias.double().abs()[None, :]
+    if c_old is not None:
+        r.y = r.y + c_old.double()
+        r.s = r.s + c_old.double().abs()
+    r.colsum, r.colsum_s = A.sum(1), A.abs().sum(1)
+    return epilogue_ref64(r, epi, pre=pre, keep=keep, drop_p=drop_p)
+
+
+def epilogue_ref64(r, epi, *, pre=None, keep=None, drop_p=0.0):
+    """Fill act / lin / add / scale of a GemmRef whose y and s are set (gemm_ref64's second half; the implicit
+    convolutions enter here with F.conv1d's y)."""
+    r.epi = epi
+    r.scale = torch.ones_like(r.y)
+    if keep is not None:
+        r.scale = keep.to(r.y.dtype) / (1.0 - float(np.float32(drop_p)))
+    r.act = r.lin = r.add = None
+    if epi in (EPI_GELU, EPI_GELU_ONLY):
+        r.act = torch.nn.functional.gelu(r.y) * r.scale
+        r.lin = gelu_grad64(r.y).abs()
+        r.add = torch.zeros_like(r.y)
+    elif epi == EPI_DGELU:
+        g = gelu_grad64(pre.double())
+        r.act = r.y * g * r.scale
+        r.lin = g.abs()
+        r.add = GEMM_DGELU_REL * r.y.abs()
+    return r
+
+
+def gemm_bound(r, which, C, bf16_out, gelu_abs=GEMM_GELU_ABS):
+    """(reference, per-element bound) of output `which` of a GemmRef: "y" (store / accumulate / the pre-activation
+    of EPI_GELU): C 2^-24 s; "act": (lin C 2^-24 s + a) scale with a = gelu_abs for the GELU outputs and 2e-6 |y| for
+    dGELU. A bf16 output adds one rounding with a factor 2, 2^-8 |ref|."""
+    if which == "y":
+        ref, b = r.y, C * U24 * r.s
+    else:
+        ref = r.act
+        b = (r.lin * (C * U24) * r.s + (r.add if r.epi == EPI_DGELU else gelu_abs)) * r.scale
+    if bf16_out:
+        b = b + 2.0 ** -8 * ref.abs()
+    return ref, b
+
+
+def gemm_eval_fp32(A, B, *, bias=None, alpha=1.0, c_old=None, ksplit=0):
+    """The same value in fp32 arithmetic: A [M, K], B [N, K] float32 (the rounded operands; products of two bf16 are
+    exact in fp32). Each split-K slice of ksplit (0: one slice) accumulates its 64-wide K tiles in order; the slices are
+    added in order; then alpha, the bias and c_old."""
+    M, K = A.shape
+    ks = ksplit or K
+    tot = torch.zeros(M, B.shape[0], dtype=torch.float32)
+    for k0 in range(0, K, ks):
+        acc = torch.zeros_like(tot)
+        for k in range(k0, min(K, k0 + ks), 64):
+            k1 = min(K, k0 + ks, k + 64)
+            acc = acc + A[:, k:k1] @ B[:, k:k1].t()
+        tot = tot + acc
+    y = tot * np.float32(alpha)
+    if bias is not None:
+        y = y + bias.float()[None, :]
+    if c_old is not None:
+        y = y + c_old.float()
+    return y
+
+
+_GEMM_OPERANDS = {}
+
+
+def gemm_operands(M, N, K, dt, a_f32=False):
+    """Seeded operands of one (M, N, K): A [M, K] and B [N, K] = randn times a per-row (A) and a per-column (B, the
+    output's columns) power of two from 2^-6 .. 2^6, rounded to the compute dtype dt ("f32" / "bf16"; a_f32: A stays
+    float32, the kernel rounds it to bf16 while staging), so that small rows and columns cannot hide under large ones.
+    bias = randn times the column scale (f32). c_old (the accumulate epilogue's previous C) = randn times both scales,
+    pre (the dGELU epilogue's saved pre-activation) = 2 randn, cs_old = randn times the row scale. CPU tensors, cached."""
+    key = (M, N, K, dt, a_f32)
+    if key not in _GEMM_OPERANDS:
+        gen = torch.Generator().manual_seed(1000003 * M + 1009 * N + K)
+        r = torch.pow(2.0, torch.randint(-6, 7, (M,), generator=gen).float())
+        c = torch.pow(2.0, torch.randint(-6, 7, (N,), generator=gen).float())
+        td = torch.float32 if dt == "f32" else torch.bfloat16
+        A = torch.randn(M, K, generator=gen) * r[:, None]
+        B = (torch.randn(N, K, generator=gen) * c[:, None]).to(td)
+        A = A if a_f32 else A.to(td)
+        bias = torch.randn(N, generator=gen) * c
+        c_old = torch.randn(M, N, generator=gen) * r[:, None] * c[None, :]
+        pre = 2.0 * torch.randn(M, N, generator=gen)
+        cs_old = torch.randn(M, generator=gen) * r
+        _GEMM_OPERANDS[key] = dict(A=A, B=B, bias=bias, c_old=c_old, pre=pre, cs_old=cs_old)
+    return _GEMM_OPERANDS[key]
+
+
+def gemm_logical64(ops_, dt, device=None):
+    """The logical float64 operands of a gemm_operands() entry: an f32-stored A of a bf16 GEMM rounds to bf16 first."""
+    A, B = ops_["A"], ops_["B"]
+    if dt == "bf16":
+        A = A.to(torch.bfloat16)
+    if device is not None:
+        A, B = A.to(device), B.to(device)
+    return A.double(), B.double()
+
+
+def small_splits(M, N, K, dt):
+    """(slices, K per slice) of fddm_gemm's register-staged kernel for an f32 store / accumulate (csrc/gemm.hip)."""
+    kstep = 64 if dt == "bf16" else 32
+    tiles = ((M + 127) // 128) * ((N + 127) // 128)
+    if tiles >= 512 or K < 8 * kstep:
+        return 1, 0
+    nz = max(1, min((512 + tiles - 1) // tiles, K // max(kstep, 512), 64))
+    if nz == 1:
+        return 1, 0
+    ks = ((K + nz - 1) // nz + kstep - 1) // kstep * kstep
+    return (K + ks - 1) // ks, ks
+
+
+def g128_splits(M, N, K):
+    """(slices, K per slice) of the 128x128 LDS-DMA kernel for an f32 store / accumulate (fddm_gemm's dispatch)."""
+    t = ((M + 127) // 128) * ((N + 127) // 128)
+    if t >= 192 or K < 4096:
+        return 1, 0
+    nz = max(1, min((256 + t - 1) // t, K // 2048))
+    if nz == 1:
+        return 1, 0
+    ks = ((K + nz - 1) // nz + 63) // 64 * 64
+    return (K + ks - 1) // ks, ks
+
+
+def _case(fam, dt, M, N, K, epi, out, *, a_kc=1, b_kc=1, bias=True, alpha=1.0, p=0.0, pad=0, colsum=False, Mi=0,
+          a_f32=False, cap=0, expect=None):
+    nz, ks = 1, 0
+    if out == "f32" and epi in (EPI_STORE, EPI_ACC) and not Mi:
+        if fam == "small":
+            nz, ks = small_splits(M, N, K, dt)
+        elif fam == "128":
+            nz, ks = g128_splits(M, N, K)
+    if fam == "128" and bias and (epi == EPI_ACC or nz > 1):
+        # the ring kernel's accumulate epilogue takes no bias: fddm_gemm must send these to the register-staged kernel
+        expect = "small"
+        nz, ks = small_splits(M, N, K, dt)
+    c = dict(fam=fam, dt=dt, M=M, N=N, K=K, epi=epi, out=out, a_kc=a_kc, b_kc=b_kc, bias=bias, alpha=alpha, p=p, pad=pad,
+             colsum=colsum, Mi=Mi, a_f32=a_f32, cap=cap, splits=nz, ksplit=ks, expect=expect or fam)
+    c["id"] = (f"{fam}-{dt}{'-af32' if a_f32 else ''}-{M}x{N}x{K}-{'k' if a_kc else 'm'}{'k' if b_kc else 'm'}-"
+               f"{EPI_NAMES[epi]}-{out}" + ("-bias" if bias else "") + (f"-a{GEMM_ALPHAS.index(alpha)}" if alpha != 1.0 else "")
+               + (f"-p{p}" if p else "") + (f"-pad{pad}" if pad else "") + ("-colsum" if colsum else "")
+               + (f"-Mi{Mi}" if Mi else "") + (f"-cap{cap}" if cap else "") + (f"-z{nz}" if nz > 1 else "")
+               + (f"-not{fam}" if expect else ""))
+    return c
+
+
+LAYOUTS = ((1, 1), (1, 0), (0, 0), (0, 1))
+
+
+def _epis(dt, which):
+    """(epi, out, p) of every epilogue in `which` for compute dtype dt; the GELU family writes the compute dtype."""
+    o = []
+    for e in which:
+        if e == "store_f32":
+            o.append((EPI_STORE, "f32", 0.0))
+        elif e == "store_bf16":
+            if dt == "bf16":
+                o.append((EPI_STORE, "bf16", 0.0))
+        elif e == "acc":
+            o.append((EPI_ACC, "f32", 0.0))
+        elif e == "gelu_only":
+            o.append((EPI_GELU_ONLY, dt, 0.0))
+        elif e == "gelu":
+            o += [(EPI_GELU, dt, 0.0), (EPI_GELU, dt, 0.1)]
+        elif e == "dgelu":
+            o += [(EPI_DGELU, dt, 0.0), (EPI_DGELU, dt, 0.1)]
+    return o
+
+
+ALL_EPIS = ("store_f32", "store_bf16", "gelu", "gelu_only", "dgelu", "acc")
+
+
+def gemm_cases():
+    """Every fddm_gemm case of tests/test_gpu_gemm.py: the smallest shapes at which each mechanism of each kernel family
+    exists (the reasons stand next to the shapes). alpha and bias cycle so that every (family, layout, epilogue) meets
+    all three alphas and both a bias and none."""
+    cs = []
+    count = {}
+
+    def cyc(out, *key):
+        # alpha = 1/1536 meets a bias only where the output is f32: under a bf16 output's rounding of a bias-sized
+        # value no reference could tell what happened to a product 1536 times smaller
+        n = count[key] = count.get(key, -1) + 1       # one cycle of 6 per (family, layout / epilogue)
+        al = GEMM_ALPHAS[n % 3]
+        return dict(alpha=al, bias=n % 2 == 0 and not (out == "bf16" and al == GEMM_ALPHAS[2]))
+
+    # ---- small: the register-staged 128x128 kernel (gemm_kernel), forced
+    for dt in ("f32", "bf16"):
+        for a_kc, b_kc in LAYOUTS:
+            # one partial K-step, N < 128 | 3 x 2 tiles, ragged last K-step (bf16 64-wide, f32 32-wide)
+            for M, N, K in ((136, 72, 40), (264, 136, 200)):
+                cs.append(_case("small", dt, M, N, K, EPI_STORE, dt, a_kc=a_kc, b_kc=b_kc, **cyc(dt, "s", EPI_STORE)))
+        # N % 8 != 0, ldc = 77: the scalar store path of every epilogue, rows unaligned
+        for epi, out, p in _epis(dt, ALL_EPIS):
+            cs.append(_case("small", dt, 136, 75, 200, epi, out, p=p, pad=2, **cyc(out, "s", epi)))
+        # ... and zero2d's unaligned-row and tail branches under a 2-slice split-K store
+        cs.append(_case("small", dt, 136, 75, 1096, EPI_STORE, "f32", pad=2, **cyc("f32", "s", EPI_STORE)))
+        # split-K, K = 1096 = 576 + 520: 2 slices, the second ragged; bias on slice 0 only; ldc > N
+        for epi in (EPI_STORE, EPI_ACC):
+            for al in GEMM_ALPHAS[:2]:
+                cs.append(_case("small", dt, 136, 72, 1096, epi, "f32", bias=True, alpha=al, pad=8))
+            cs.append(_case("small", dt, 136, 72, 1096, epi, "f32", a_kc=0, b_kc=0, colsum=True, **cyc("f32", "s", epi)))
+        cs.append(_case("small", dt, 136, 72, 200, EPI_STORE, "f32", a_kc=0, b_kc=0, colsum=True, bias=False))
+        cs.append(_case("small", dt, 136, 72, 200, EPI_ACC, "f32", a_kc=0, b_kc=0, colsum=True, bias=True))
+        # batched A rows: Mi = 50, batch stride > Mi * lda
+        cs.append(_case("small", dt, 150, 72, 200, EPI_STORE, dt, Mi=50, **cyc(dt, "s", EPI_STORE)))
+        cs.append(_case("small", dt, 150, 72, 1096, EPI_STORE, "f32", Mi=50, **cyc("f32", "s", EPI_STORE)))   # batched: never split
+        # every epilogue on 3 x 2 tiles
+        for epi, out, p in _epis(dt, ALL_EPIS):
+            cs.append(_case("small", dt, 264, 136, 200, epi, out, p=p, **cyc(out, "s", epi)))
+    for a_kc, b_kc in LAYOUTS:   # f32-stored A, bf16 MFMA
+        cs.append(_case("small", "bf16", 136, 72, 200, EPI_STORE, "bf16", a_kc=a_kc, b_kc=b_kc, a_f32=True, **cyc("bf16", "s", "af32")))
+
+    # ---- 128: the 4-stage LDS-DMA ring (gemm128_kernel), forced, bf16
+    # one tile | 1..5 K-tiles against the 3-ahead ring prologue, tiles shifted in both dimensions | 4 x 3 tiles
+    shapes = [(128, 128, 64)] + [(200, 136, K) for K in (64, 128, 192, 256, 320)] + [(392, 264, 128)]
+    per_layout = {(1, 1): ALL_EPIS, (1, 0): ("store_f32", "store_bf16", "dgelu", "acc"), (0, 0): ("store_f32", "acc")}
+    for (a_kc, b_kc), which in per_layout.items():
+        for M, N, K in shapes:
+            for epi, out, p in _epis("bf16", which):
+                kw = cyc(out, a_kc, b_kc, epi, p)
+                kw["bias"] = kw["bias"] and epi != EPI_ACC      # the ring's accumulate epilogue takes no bias (below)
+                cs.append(_case("128", "bf16", M, N, K, epi, out, a_kc=a_kc, b_kc=b_kc, p=p, pad=8 if M == 392 else 0,
+                                colsum=(a_kc == 0 and K in (64, 192)), **kw))
+    # ragged token count: mask_set and the buffer range check, fused colsum; one ragged K-tile alone
+    for epi in (EPI_STORE, EPI_ACC):
+        for M, N, K in ((200, 136, 203), (128, 128, 8)):
+            kw = cyc("f32", 0, 0, epi, 0.0)
+            kw["bias"] = kw["bias"] and epi != EPI_ACC
+            cs.append(_case("128", "bf16", M, N, K, epi, "f32", a_kc=0, b_kc=0, colsum=True, **kw))
+    # split-K: 2 slices (KC: 2112 + 2048; MC: 2112 + 1988, ragged), overlap added once. With a bias the call must
+    # leave this family for the register-staged kernel (8 slices there), which adds the bias on slice 0 only
+    for (a_kc, b_kc), K in (((1, 1), 4160), ((0, 0), 4100)):
+        for epi in (EPI_STORE, EPI_ACC):
+            for bias in (True, False):
+                cs.append(_case("128", "bf16", 200, 136, K, epi, "f32", a_kc=a_kc, b_kc=b_kc, bias=bias, pad=8,
+                                alpha=GEMM_ALPHAS[len(cs) % 3], colsum=a_kc == 0))
+    # accumulate with bias, one slice, all three alphas: off this family as well
+    for al in GEMM_ALPHAS:
+        cs.append(_case("128", "bf16", 200, 136, 192, EPI_ACC, "f32", bias=True, alpha=al))
+
+    # ---- 256: the persistent 256x256 kernel (gemm256_kernel), forced, bf16 KC/KC, alpha = 1
+    e256 = [(EPI_STORE, "bf16", 0.0), (EPI_STORE, "f32", 0.0), (EPI_GELU, "bf16", 0.0), (EPI_GELU, "bf16", 0.1),
+            (EPI_GELU_ONLY, "bf16", 0.0)]
+    i = 0
+    # one tile, 2 / 3 / 4 / 9 K-tiles | 2 x 3 tiles shifted in both dimensions | 5 x 4 = 20 tiles: on 8 workgroups 2 or 3
+    # tiles each and a last tile-row group of 1 < GM rows; uncapped one tile per workgroup
+    for M, N, K, cap in [(256, 256, K, 0) for K in (128, 192, 256, 576)] + [(264, 520, 192, 0), (1100, 776, 128, 8),
+                                                                            (1100, 776, 128, 0)]:
+        for epi, out, p in e256:
+            i += 1
+            cs.append(_case("256", "bf16", M, N, K, epi, out, p=p, bias=i % 2 == 0, pad=8 if (i // 2) % 2 else 0, cap=cap))
+    cs.append(_case("256", "bf16", 256, 256, 128, EPI_STORE, "bf16", alpha=-0.375, expect="small"))
+
+    # ---- big: the 256x128 LDS-DMA kernel (gemm_big_kernel), forced, bf16 output
+    # 15 x 17 = 255 tiles ragged in both dimensions, XCD remap remainder 7, 1..4 K-steps against the 3-slot ring
+    for K in (64, 128, 192, 256):
+        for epi, out, p in ((EPI_STORE, "bf16", 0.0), (EPI_GELU, "bf16", 0.1), (EPI_GELU_ONLY, "bf16", 0.0)):
+            cs.append(_case("big", "bf16", 3592, 2056, K, epi, out, p=p, bias=True, alpha=GEMM_ALPHAS[len(cs) % 2]))
+    seen, out = set(), []
+    for c in cs:       # the explicit cases may repeat one the cycle produced
+        if c["id"] not in seen:
+            seen.add(c["id"])
+            out.append(c)
+    return out
+
+
+def rope_bwd_ref64(P, cos, sin, L, magnitude=False):
+    """The decoder's RoPE backward (oracle rope_apply's transpose) of P [M, d] (float64), row m at position m % L:
+    with a = P[:, :d/2], b = P[:, d/2:]: out[:, 0::2] = a cos[:, 0::2] + b sin[:, 0::2],
+    out[:, 1::2] = -a sin[:, 1::2] + b cos[:, 1::2]. magnitude=True adds every term (P, cos, sin given as magnitudes):
+    the error scale of the same sum."""
+    M, d = P.shape
+    pos = torch.arange(M, device=P.device) % L
+    c, s = cos.double()[pos], sin.double()[pos]
+    a, b = P[:, : d // 2], P[:, d // 2:]
+    out = torch.empty_like(P)
+    out[:, 0::2] = a * c[:, 0::2] + b * s[:, 0::2]
+    out[:, 1::2] = (a if magnitude else -a) * s[:, 1::2] + b * c[:, 1::2]
+    return out
+
+
+# implicit conv (fddm_conv1d_gemm): name -> geometry. x [Bn, Tin, G Cg] channels-last, w [G N, Cg, taps] as F.conv1d takes it
+CONV_CASES = {
+    # taps outside the input at both ends (cpad 2; the last frame's last tap is at Tin), 2 groups, 396 rows = 3 tiles + 12
+    "small": dict(fam="small", G=2, Cg=16, N=24, taps=5, stride=2, cpad=2, Bn=3, Tin=263, Tout=132),
+    # 260 rows x 264 columns: 2 x 2 shifted 256x256 tiles, 6 K-tiles over 3 taps, frames of both utterances in one tile
+    "256": dict(fam="256", G=1, Cg=128, N=264, taps=3, stride=2, cpad=0, Bn=2, Tin=261, Tout=130),
+    # 3848 x 1928: 16 x 16 = 256 tiles of 256x128 (ragged in both), one K-step per tap
+    "big": dict(fam="big", G=1, Cg=64, N=1928, taps=3, stride=2, cpad=0, Bn=4, Tin=1925, Tout=962),
+}
+
+
+def conv_operands(name, dt):
+    """x [Bn, Tin, G Cg] = randn times a power of two per frame, w [G N, Cg, taps] = randn times a power of two per
+    output channel, both rounded to dt; bias = randn times the channel scale."""
+    g = CONV_CASES[name]
+    gen = torch.Generator().manual_seed(77 + g["Tin"])
+    td = torch.float32 if dt == "f32" else torch.bfloat16
+    r = torch.pow(2.0, torch.randint(-6, 7, (g["Bn"], g["Tin"], 1), generator=gen).float())
+    c = torch.pow(2.0, torch.randint(-6, 7, (g["G"] * g["N"],), generator=gen).float())
+    x = (torch.randn(g["Bn"], g["Tin"], g["G"] * g["Cg"], generator=gen) * r).to(td)
+    w = (torch.randn(g["G"] * g["N"], g["Cg"], g["taps"], generator=gen) * c[:, None, None]).to(td)
+    bias = torch.randn(g["G"] * g["N"], generator=gen) * c
+    return x, w, bias
+
+
+def conv_im2col(name, x, w):
+    """The implicit GEMM's logical operands per group: A_z [Bn Tout, taps Cg] (row = frame, k = tap * Cg + c, zeros for
+    taps outside the input) and B_z [N, taps Cg], in the dtype of x / w."""
+    g = CONV_CASES[name]
+    xp = torch.nn.functional.pad(x, (0, 0, g["cpad"], g["cpad"]))
+    win = xp.unfold(1, g["taps"], g["stride"])[:, : g["Tout"]]               # [Bn, Tout, G Cg, taps]
+    out = []
+    for z in range(g["G"]):
+        A = win[:, :, z * g["Cg"]:(z + 1) * g["Cg"], :].permute(0, 1, 3, 2).reshape(g["Bn"] * g["Tout"], -1)
+        B = w[z * g["N"]:(z + 1) * g["N"]].permute(0, 2, 1).reshape(g["N"], -1)
+        out.append((A, B))
+    return out
+
+
+def conv_ref(name, x, w, bias, dtype=torch.float64):
+    """F.conv1d of the case in dtype and its error scale |x| * |w| + |bias|, both [Bn * Tout, G N] (rows = frames);
+    x, w, bias on any device."""
+    g = CONV_CASES[name]
+    F = torch.nn.functional
+    xt = x.to(dtype).transpose(1, 2)
+    y = F.conv1d(xt, w.to(dtype), bias.to(dtype), stride=g["stride"], padding=g["cpad"], groups=g["G"])
+    s = F.conv1d(xt.abs(), w.to(dtype).abs(), bias.to(dtype).abs(), stride=g["stride"], padding=g["cpad"], groups=g["G"])
+    assert y.shape[-1] == g["Tout"], (y.shape, g["Tout"])
+    return (y.transpose(1, 2).reshape(g["Bn"] * g["Tout"], -1), s.transpose(1, 2).reshape(g["Bn"] * g["Tout"], -1))
