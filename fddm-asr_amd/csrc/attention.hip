@@ -2458,6 +2458,8 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
           const long nh = (long)a.B * a.H, ncu = attn_cu_count();
           const long load8 = (nh * ((a.Lq + 255) / 256) + ncu - 1) / ncu * 256;
           const long load7 = (nh * ((a.Lq + 127) / 128) + ncu - 1) / ncu * 128;
+          // a key extent (fddm_attn_fwd_kx) always takes fwd7: its KX build bounds the tile loop, fwd8 has none
+          if (a.key_len) return attn7_fwd(a, s);
           return (g_attn_v6 == 3 || (g_attn_v6 != 4 && load8 > load7)) ? attn7_fwd(a, s) : attn8_fwd(a, s);
         }
         const size_t lds = (size_t)2 * 2 * 64 * 128 + (size_t)LkP * 4 +
@@ -2594,12 +2596,14 @@ FDDM_API int fddm_attn_set_kernels(int v6) {
 }
 
 // Forward. Q/K/V/O: element (b, pos, h, d) at base + (b*L + pos)*stride + h*64 + d.
-FDDM_API int fddm_attn_fwd(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv, void* O,
-                           long so, float* lse, const unsigned char* key_keep, const float* gate, const float* table,
-                           int B, int H, int Lq, int Lk, float scale, float drop_p, unsigned long long seed,
-                           unsigned long long stream, unsigned long long* drop_bits, int drop_bits_ready, void* hs) {
+static int attn_fwd_impl(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv, void* O,
+                         long so, float* lse, const unsigned char* key_keep, const int* key_len, const float* gate,
+                         const float* table, int B, int H, int Lq, int Lk, float scale, float drop_p,
+                         unsigned long long seed, unsigned long long stream, unsigned long long* drop_bits,
+                         int drop_bits_ready, void* hs) {
   if (table && !gate) return (int)hipErrorInvalidValue;  // a bias table without its gate: no kernel takes that
   AttnArgs a{};
+  a.key_len = key_len;
   a.dbits = (uint64_t*)drop_bits;
   a.bits_ready = drop_bits_ready;
   a.Q = Q; a.K = K; a.V = V; a.Out = O; a.lse = lse;
@@ -2607,6 +2611,24 @@ FDDM_API int fddm_attn_fwd(int dtype, const void* Q, long sq, const void* K, lon
   a.key_keep = key_keep; a.gate = gate; a.table = table;
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.scale = scale; a.seed = seed; a.stream = stream; a.seed_off = g_seed_off;
   return attn_dispatch(0, dtype, a, drop_p, hs);
+}
+FDDM_API int fddm_attn_fwd(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv, void* O,
+                           long so, float* lse, const unsigned char* key_keep, const float* gate, const float* table,
+                           int B, int H, int Lq, int Lk, float scale, float drop_p, unsigned long long seed,
+                           unsigned long long stream, unsigned long long* drop_bits, int drop_bits_ready, void* hs) {
+  return attn_fwd_impl(dtype, Q, sq, K, sk, V, sv, O, so, lse, key_keep, nullptr, gate, table, B, H, Lq, Lk, scale,
+                       drop_p, seed, stream, drop_bits, drop_bits_ready, hs);
+}
+// Forward with the key extents of fddm_key_extent next to the key-padding mask: bf16 with Lk <= 1024 runs fwd7's
+// length-bounded build (batch entry b's key tiles stop at key_len[b]); every other case runs the key_keep path.
+FDDM_API int fddm_attn_fwd_kx(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv,
+                              void* O, long so, float* lse, const unsigned char* key_keep, const int* key_len,
+                              const float* gate, const float* table, int B, int H, int Lq, int Lk, float scale,
+                              float drop_p, unsigned long long seed, unsigned long long stream,
+                              unsigned long long* drop_bits, int drop_bits_ready, void* hs) {
+  if (!key_keep || !key_len) return (int)hipErrorInvalidValue;
+  return attn_fwd_impl(dtype, Q, sq, K, sk, V, sv, O, so, lse, key_keep, key_len, gate, table, B, H, Lq, Lk, scale,
+                       drop_p, seed, stream, drop_bits, drop_bits_ready, hs);
 }
 
 // u64 words per site of the keep-bit buffer: room for either storage layout (the round-4 words [B*H][ntiles][Lq] or
@@ -2659,26 +2681,46 @@ FDDM_API int fddm_attn_fwd_relgate(const void* Q, long sq, const void* K, long s
 // WavLM forward with the gate computed in the kernel from the attention input x itself (bf16 rows, stride sx; the
 // head's 64 inputs against gw = [sum of gru_rel_pos_linear rows 0-3 | rows 4-7 | their bias sums], 130 floats): the
 // Q|K|V projection needs no extra gate columns and no separate gate pass runs.
-FDDM_API int fddm_attn_fwd_relgate_x(const void* Q, long sq, const void* K, long sk, const void* V, long sv, void* O,
-                                     long so, const void* x, long sx, const float* gw, const float* gconst,
-                                     const float* table, int B, int H, int Lq, int Lk, float scale, void* hs) {
+static int attn_relgate_x_impl(const void* Q, long sq, const void* K, long sk, const void* V, long sv, void* O,
+                               long so, const void* x, long sx, const float* gw, const float* gconst,
+                               const float* table, const unsigned char* key_keep, const int* key_len, int B, int H,
+                               int Lq, int Lk, float scale, void* hs) {
   if (!x || !gw || !gconst || !table || (((uintptr_t)x) & 15) || (((uintptr_t)gw) & 15) || sx % 8)
     return (int)hipErrorInvalidValue;
   AttnArgs a{};
+  a.key_keep = key_keep; a.key_len = key_len;
   a.Q = Q; a.K = K; a.V = V; a.Out = O;
   a.sq = sq; a.sk = sk; a.sv = sv; a.so = so;
   a.gx = x; a.sgx = sx; a.gw = gw; a.gconst = gconst; a.table = table;
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.scale = scale;
   return attn_dispatch(0, FDDM_BF16, a, 0.f, hs);
 }
+FDDM_API int fddm_attn_fwd_relgate_x(const void* Q, long sq, const void* K, long sk, const void* V, long sv, void* O,
+                                     long so, const void* x, long sx, const float* gw, const float* gconst,
+                                     const float* table, int B, int H, int Lq, int Lk, float scale, void* hs) {
+  return attn_relgate_x_impl(Q, sq, K, sk, V, sv, O, so, x, sx, gw, gconst, table, nullptr, nullptr, B, H, Lq, Lk,
+                             scale, hs);
+}
+// The same with WavLM's key-padding mask (HF modeling_wavlm.py:399-402, 569-596: padded frames are no keys) and its
+// key extents: fwd7's REL build, length-bounded for Lk <= 1024 (longer: fwd5 with the mask alone).
+FDDM_API int fddm_attn_fwd_relgate_x_kx(const void* Q, long sq, const void* K, long sk, const void* V, long sv,
+                                        void* O, long so, const void* x, long sx, const float* gw,
+                                        const float* gconst, const float* table, const unsigned char* key_keep,
+                                        const int* key_len, int B, int H, int Lq, int Lk, float scale, void* hs) {
+  if (!key_keep || !key_len) return (int)hipErrorInvalidValue;
+  return attn_relgate_x_impl(Q, sq, K, sk, V, sv, O, so, x, sx, gw, gconst, table, key_keep, key_len, B, H, Lq, Lk,
+                             scale, hs);
+}
 
 // Backward: dQ (query-owned kernel) and dK/dV (key-owned kernel). lse from the forward.
-FDDM_API int fddm_attn_bwd(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv,
-                           const void* O, long so, const void* dO, long sdo, const float* lse, void* dQ, long sdq,
-                           void* dK, long sdk, void* dV, long sdv, float* delta_ws, const unsigned char* key_keep,
-                           int B, int H, int Lq, int Lk, float scale, float drop_p, unsigned long long seed,
-                           unsigned long long stream, const unsigned long long* drop_bits, void* hs) {
+static int attn_bwd_impl(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv,
+                         const void* O, long so, const void* dO, long sdo, const float* lse, void* dQ, long sdq,
+                         void* dK, long sdk, void* dV, long sdv, float* delta_ws, const unsigned char* key_keep,
+                         const int* key_len, int B, int H, int Lq, int Lk, float scale, float drop_p,
+                         unsigned long long seed, unsigned long long stream, const unsigned long long* drop_bits,
+                         void* hs) {
   AttnArgs a{};
+  a.key_len = key_len;
   a.dbits = (uint64_t*)drop_bits;
   a.delta = delta_ws;
   a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.lse = (float*)lse;
@@ -2696,4 +2738,24 @@ FDDM_API int fddm_attn_bwd(int dtype, const void* Q, long sq, const void* K, lon
   int e = attn_dispatch(1, dtype, a, drop_p, hs);
   if (e) return e;
   return attn_dispatch(2, dtype, a, drop_p, hs);
+}
+FDDM_API int fddm_attn_bwd(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv,
+                           const void* O, long so, const void* dO, long sdo, const float* lse, void* dQ, long sdq,
+                           void* dK, long sdk, void* dV, long sdv, float* delta_ws, const unsigned char* key_keep,
+                           int B, int H, int Lq, int Lk, float scale, float drop_p, unsigned long long seed,
+                           unsigned long long stream, const unsigned long long* drop_bits, void* hs) {
+  return attn_bwd_impl(dtype, Q, sq, K, sk, V, sv, O, so, dO, sdo, lse, dQ, sdq, dK, sdk, dV, sdv, delta_ws, key_keep,
+                       nullptr, B, H, Lq, Lk, scale, drop_p, seed, stream, drop_bits, hs);
+}
+// Backward with the key extents: the 32x32x16 kernels' length-bounded builds (bwdf7, dq7 + dkv7) where they run;
+// dK / dV rows at or past an entry's extent are exact zeros. Every other case runs the key_keep path.
+FDDM_API int fddm_attn_bwd_kx(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv,
+                              const void* O, long so, const void* dO, long sdo, const float* lse, void* dQ, long sdq,
+                              void* dK, long sdk, void* dV, long sdv, float* delta_ws, const unsigned char* key_keep,
+                              const int* key_len, int B, int H, int Lq, int Lk, float scale, float drop_p,
+                              unsigned long long seed, unsigned long long stream,
+                              const unsigned long long* drop_bits, void* hs) {
+  if (!key_keep || !key_len) return (int)hipErrorInvalidValue;
+  return attn_bwd_impl(dtype, Q, sq, K, sk, V, sv, O, so, dO, sdo, lse, dQ, sdq, dK, sdk, dV, sdv, delta_ws, key_keep,
+                       key_len, B, H, Lq, Lk, scale, drop_p, seed, stream, drop_bits, hs);
 }

@@ -183,11 +183,37 @@ long attn7_drop_words(int B, int H, int Lq, int Lk) {  // lane masks + per-lane 
 // scalar f32, here and in the decoder's fwd7, tools/r06_t48.sh). The gate per query
 // comes from a precomputed row, from the Q|K|V projection's 8 extra columns, or from the attention input x through
 // the folded GRU weights (lanes l and l ^ 32 each take 32 of the head's 64 inputs).
+// KX builds: batch entry b's key extent klen = a.key_len[b] clamped to [0, Lk] and its live 64-key tiles
+// nlive = max(1, ceil(klen / 64)). A fully masked entry (klen 0) keeps one tile live: fwd7 / dq7 find no kept key in
+// it and run no tile (NaN output and LSE rows, as without the bound); the key-owned kernels run the first tile's keys
+// as padding (the dK / dV rows of the waves / workgroup that hold it take the NaN of the entry's LSE, as without the
+// bound) and store zeros past them, where the key_keep path leaves NaN in every row of such an entry
+__device__ __forceinline__ void live_tiles(const AttnArgs& a, int b, int& klen, int& nlive) {
+  klen = min(max(__builtin_amdgcn_readfirstlane(a.key_len[b]), 0), a.Lk);
+  nlive = max(1, (klen + 63) >> 6);
+}
+// zeros to rows row0 + [0, nrows) (< Lk) of head h's dK and dV slices: the keys past a batch entry's extent (nthr
+// threads, 16 bytes per store)
+__device__ __forceinline__ void zero_dkv_rows(const AttnArgs& a, int b, int h, int row0, int nrows, int tid, int nthr) {
+  bf16_t* dKb = (bf16_t*)a.dK + (long)b * a.Lk * a.sdk + h * DH;
+  bf16_t* dVb = (bf16_t*)a.dV + (long)b * a.Lk * a.sdv + h * DH;
+  for (int i = tid; i < nrows * 8; i += nthr) {
+    const int row = row0 + (i >> 3), c = i & 7;
+    if (row < a.Lk) {
+      *(uint4*)(dKb + (long)row * a.sdk + c * 8) = make_uint4(0u, 0u, 0u, 0u);
+      *(uint4*)(dVb + (long)row * a.sdv + c * 8) = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+}
 #ifndef A7_FWD_WPS
 #define A7_FWD_WPS 3  // waves per SIMD the forward's register allocation targets
 #endif
-template <int DM, int MK, bool REL = false>
+// KX (with MK 2): the key-tile loop, the mask build and the active-tile mask of batch entry b stop at its key extent
+// a.key_len[b] (live_tiles above); the keep-bit words keep the layout of the full key range, skipped tiles' words are
+// not read.
+template <int DM, int MK, bool REL = false, bool KX = false>
 __global__ void __launch_bounds__(256, A7_FWD_WPS) fwd7_kernel(AttnArgs a) {
+  static_assert(!KX || MK == 2, "the key extent comes with a key-padding mask");
   constexpr bool DROP = DM != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char sm7[];
   const int ntiles = (a.Lk + 63) >> 6, LkP = ntiles * 64;
@@ -243,6 +269,8 @@ __global__ void __launch_bounds__(256, A7_FWD_WPS) fwd7_kernel(AttnArgs a) {
       qf[ks] = scale_frag(make_uint4(x.x & zm, x.y & zm, x.z & zm, x.w & zm), sl2);
     }
   }
+  int klen = a.Lk, nlive = ntiles;
+  if constexpr (KX) live_tiles(a, b, klen, nlive);
   float g2 = 0.f;  // REL: the query's gate in log2 units
   int boff = 0;    // REL: the lane's float offset of its bias quads in the shifted copies (key offset 0)
   if constexpr (REL) {
@@ -287,24 +315,26 @@ __global__ void __launch_bounds__(256, A7_FWD_WPS) fwd7_kernel(AttnArgs a) {
     const int CL = LkP + 160, qbase = bxi * 128;
     const float* tabh = a.table + (long)h * (2 * a.Lk - 1);
     const long off0 = (long)(a.Lk - 1) - (qbase + 127);
-    for (int i = tid; i < 2 * CL; i += 256) {
-      const int c = i >= CL ? 1 : 0;
-      const long ti = off0 + (i - c * CL) + c;
-      bcp[i] = (ti >= 0 && ti < 2L * a.Lk - 1) ? tabh[ti] : 0.f;
+    // KX: only the entries the live tiles read (a lane's last read ends below entry 64 nlive + 127 of its copy)
+    const int CU = KX ? 64 * nlive + 160 : CL;
+    for (int i = tid; i < 2 * CU; i += 256) {
+      const int c = i >= CU ? 1 : 0, e = i - c * CU;
+      const long ti = off0 + e + c;
+      bcp[c * CL + e] = (ti >= 0 && ti < 2L * a.Lk - 1) ? tabh[ti] : 0.f;
     }
     const int jq = qbase + 127 - q;  // key k of this query sits at slice entry k + jq
     boff = (jq & 1) * CL + (jq & ~1) + 4 * hh;
   }
-  unsigned tmask = ntiles >= 32 ? 0xFFFFFFFFu : ((1u << ntiles) - 1u);
+  unsigned tmask = nlive >= 32 ? 0xFFFFFFFFu : ((1u << nlive) - 1u);
   if constexpr (MK != 0) {
     // thread tid owns keys 4 tid .. 4 tid + 3 (LkP <= 1024)
     bool any = false;
-    if (4 * tid < LkP) {
+    if (4 * tid < (KX ? 64 * nlive : LkP)) {
       unsigned mv[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int k = 4 * tid + j;
-        const bool ok = k < a.Lk && (MK == 1 || a.key_keep[(long)b * a.Lk + k] != 0);
+        const bool ok = k < klen && (MK == 1 || a.key_keep[(long)b * a.Lk + k] != 0);
         mv[j] = pk_bf16(1.f, ok ? 0.f : -INFINITY);
         any |= ok;
       }
@@ -500,8 +530,9 @@ __global__ void __launch_bounds__(256, A7_FWD_WPS) fwd7_kernel(AttnArgs a) {
 // dQ^T += K^T dS^T (K^T by transposed reads of the same K image). Also writes the backward's per-query row terms for
 // dkv7: nlse2 = -LSE log2(e) (-inf past Lq) and delta = rowsum(dO O) (0 past Lq), both [B*H][LqP], then the
 // pre-scaled Q' = bf16(Q scale log2(e)) (0 past Lq) as [B*H][LqP][64] bf16.
-template <int DM, int MK>
+template <int DM, int MK, bool KX = false>
 __global__ void __launch_bounds__(256, 3) dq7_kernel(AttnArgs a) {
+  static_assert(!KX || MK == 2, "the key extent comes with a key-padding mask");
   constexpr bool DROP = DM != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smq7[];
   const int ntiles = (a.Lk + 63) >> 6, LkP = ntiles * 64, LqP = (a.Lq + 63) & ~63;
@@ -569,15 +600,17 @@ __global__ void __launch_bounds__(256, 3) dq7_kernel(AttnArgs a) {
   }
   // the query's fifth-k-step operand: (-lse2 hi, -lse2 lo, 1, 0, ...) on the lanes of the first 8 k positions
   const uint4 q5 = hh ? make_uint4(0, 0, 0, 0) : make_uint4(neg_split(lse2), pk_bf16(1.f, 0.f), 0u, 0u);
-  unsigned tmask = ntiles >= 32 ? 0xFFFFFFFFu : ((1u << ntiles) - 1u);
+  int klen = a.Lk, nlive = ntiles;
+  if constexpr (KX) live_tiles(a, b, klen, nlive);
+  unsigned tmask = nlive >= 32 ? 0xFFFFFFFFu : ((1u << nlive) - 1u);
   if constexpr (MK != 0) {
     bool any = false;
-    if (4 * tid < LkP) {
+    if (4 * tid < (KX ? 64 * nlive : LkP)) {
       unsigned mv[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int k = 4 * tid + j;
-        const bool ok = k < a.Lk && (MK == 1 || a.key_keep[(long)b * a.Lk + k] != 0);
+        const bool ok = k < klen && (MK == 1 || a.key_keep[(long)b * a.Lk + k] != 0);
         mv[j] = pk_bf16(ok ? 0.f : -INFINITY, 0.f);
         any |= ok;
       }
@@ -725,8 +758,11 @@ __global__ void __launch_bounds__(256, 3) dq7_kernel(AttnArgs a) {
 // dK^T += Q'^T dS (x ln 2 = scale / sl2 at the end) with the key on the MFMA lane: the score accumulators are the B
 // operands (no LDS round trip), and the Q' / dO images serve both the row reads and the transposed reads. Keys that
 // are padding get zero gradients.
-template <int DM, bool MASK>
+// KX: workgroups whose 128 keys lie at or past the entry's live tiles store zeros and leave; keys past the extent
+// inside a live workgroup are padding.
+template <int DM, bool MASK, bool KX = false>
 __global__ void __launch_bounds__(256, 2) dkv7_kernel(AttnArgs a) {
+  static_assert(!KX || MASK, "the key extent comes with a key-padding mask");
   constexpr bool DROP = DM != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smk7[];
   const int ntiles = (a.Lk + 63) >> 6, nqt = (a.Lq + 63) >> 6, LqP = nqt * 64;
@@ -741,7 +777,16 @@ __global__ void __launch_bounds__(256, 2) dkv7_kernel(AttnArgs a) {
   const int b = bh / a.H, h = bh - b * a.H;
   const int kw0 = bxi * 128 + 32 * w;
   const int kk = kw0 + qi;
-  const bool kv = kk < a.Lk && (!MASK || a.key_keep[(long)b * a.Lk + min(kk, a.Lk - 1)] != 0);
+  int klen = a.Lk;
+  if constexpr (KX) {
+    int nlive;
+    live_tiles(a, b, klen, nlive);
+    if (bxi * 128 >= 64 * nlive) {  // workgroup-uniform, before the first DMA and barrier
+      zero_dkv_rows(a, b, h, bxi * 128, 128, tid, 256);
+      return;
+    }
+  }
+  const bool kv = kk < klen && (!MASK || a.key_keep[(long)b * a.Lk + min(kk, a.Lk - 1)] != 0);
   const bf16_t* Qb = (const bf16_t*)(a.delta + 2L * a.B * a.H * LqP) + (long)bh * LqP * DH;  // Q' rows, 128 B
   const bf16_t* dOb = (const bf16_t*)a.dO + (long)b * a.Lq * a.sdo + h * DH;
   const bf16_t* Kb = (const bf16_t*)a.K + (long)b * a.Lk * a.sk + h * DH;
@@ -928,8 +973,12 @@ __global__ void __launch_bounds__(256, 2) dkv7_kernel(AttnArgs a) {
 // loads 16 B of the next tile's Q, dO and O (8 lanes per query row), writes Q' = bf16(Q scale log2 e) (the forward's
 // operand, bit for bit) and dO into the ring, and the row's delta = rowsum(dO O) (8-lane reduction) and -LSE log2 e
 // into the row-term slots.
-template <int DM, bool MASK, int NP>
+// KX: key passes past the entry's live tiles store zeros to their dK / dV rows and do nothing else (the last live
+// pass stores dQ); in a live pass the waves whose 32 keys lie past the live tiles skip the tile body (their
+// accumulators stay zero and the dQ steps stop before their dS^T rows).
+template <int DM, bool MASK, int NP, bool KX = false>
 __global__ void __launch_bounds__(512, 1) bwdf7_kernel(AttnArgs a) {
+  static_assert(!KX || MASK, "the key extent comes with a key-padding mask");
   constexpr bool DROP = DM != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smf7[];
   const int ntiles = (a.Lk + 63) >> 6, nqt = (a.Lq + 63) >> 6;  // NP = (Lk + 255) / 256 key passes
@@ -948,6 +997,13 @@ __global__ void __launch_bounds__(512, 1) bwdf7_kernel(AttnArgs a) {
   const int nqg = (a.Lq + 31) >> 5, kbw = (kr >> 5) & 1;
   const int kt = kr & 63, rpk = 4 * ((kt >> 3) & 3) + (kt & 3), ksh = 4 * hh + 32 * ((kt >> 2) & 1);
   int kk = kr, tw = 0;  // the pass's key of the lane and the wave's 64-key tile
+  int klen = a.Lk, kend = a.Lk, npl = NP;  // the extent, the end of the live tiles' keys, the live passes
+  if constexpr (KX) {
+    int nlive;
+    live_tiles(a, b, klen, nlive);
+    kend = min(a.Lk, 64 * nlive);
+    npl = (kend + 255) >> 8;
+  }
 
   // ---- row terms of query tile uu into stage st: thread = (row tid >> 3, 16-B chunk tid & 7)
   const int pr_r = tid >> 3, pr_c = tid & 7;
@@ -983,8 +1039,10 @@ __global__ void __launch_bounds__(512, 1) bwdf7_kernel(AttnArgs a) {
       rowt[st * 128 + 64 + pr_r] = qv ? dl : 0.f;
     }
   };
+  bool wl = true;  // KX: this wave's 32 keys of the pass lie inside the live tiles (wave-uniform)
   auto kmask = [&](int uu, int st) {  // the keep masks of the wave's 32 keys for query tile uu (as dkv7)
     if constexpr (DROP) {
+      if (KX && !wl) return;  // a wave past the live tiles runs no tile body: its keep words are not fetched
       const int qgl = min(2 * uu + (lane >> 5), nqg - 1);
       dma4_sv(a.dbits, (unsigned)((lm_word(bh, nqg, ntiles, qgl, tw) + 16 * kbw) * 8 + (lane & 31) * 4),
               (const unsigned char*)(kwd + st * 512 + w * 64));
@@ -1015,12 +1073,20 @@ __global__ void __launch_bounds__(512, 1) bwdf7_kernel(AttnArgs a) {
 
 #pragma unroll
   for (int pass = 0; pass < NP; ++pass) {
+    if constexpr (KX) {
+      if (pass >= npl) {  // workgroup-uniform; the pass before ended without a barrier (it was the last live one)
+        zero_dkv_rows(a, b, h, 256 * pass, 256, tid, 512);
+        continue;
+      }
+    }
     kk = 256 * pass + kr;
     tw = min(kk >> 6, ntiles - 1);
-    const bool kv = kk < a.Lk && (!MASK || a.key_keep[(long)b * a.Lk + min(kk, a.Lk - 1)] != 0);
+    const bool kv = kk < klen && (!MASK || a.key_keep[(long)b * a.Lk + min(kk, a.Lk - 1)] != 0);
     const unsigned kvm = kv ? 0xFFFFFFFFu : 0u;
-    const int nks = (min(256, a.Lk - 256 * pass) + 15) >> 4;  // 16-key steps holding a key < Lk
-    const bool first = NP == 1 || pass == 0, last = NP == 1 || pass == NP - 1;
+    const int nks = (min(256, kend - 256 * pass) + 15) >> 4;  // 16-key steps holding a key < Lk (KX: a live key)
+    const bool first = NP == 1 || pass == 0, last = KX ? pass == npl - 1 : (NP == 1 || pass == NP - 1);
+    const bool wlive = !KX || 256 * pass + 32 * w < kend;
+    wl = wlive;
 
     // ---- prologue: the lane's K / V rows (registers) and the K image; tile 0's row terms and keep masks
     const int kc = min(kk, a.Lk - 1);
@@ -1161,7 +1227,7 @@ __global__ void __launch_bounds__(512, 1) bwdf7_kernel(AttnArgs a) {
         kmask(uu + 1, st ^ 1);
         pload(uu + 1);
       }
-      tile(st);
+      if (wlive) tile(st);
       if (more) pstore(uu + 1, st ^ 1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();  // tile uu's dS^T image complete; tile uu + 1's ring stage and row terms in place
@@ -1216,7 +1282,12 @@ int attn7_fwd(AttnArgs& a, hipStream_t s) {
   dim3 grid((a.Lq + 127) / 128, a.B * a.H);
 #define FWD7(D, M) hipLaunchKernelGGL((fwd7_kernel<D, M>), grid, dim3(256), lds, s, a)
 #define FWD7R(M) hipLaunchKernelGGL((fwd7_kernel<0, M, true>), grid, dim3(256), lds, s, a)
-  if (rel) { if (mk == 2) FWD7R(2); else if (mk == 1) FWD7R(1); else FWD7R(0); }
+  if (a.key_len && mk == 2) {  // the length-bounded builds
+    if (rel) hipLaunchKernelGGL((fwd7_kernel<0, 2, true, true>), grid, dim3(256), lds, s, a);
+    else if (dm) hipLaunchKernelGGL((fwd7_kernel<1, 2, false, true>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((fwd7_kernel<0, 2, false, true>), grid, dim3(256), lds, s, a);
+  }
+  else if (rel) { if (mk == 2) FWD7R(2); else if (mk == 1) FWD7R(1); else FWD7R(0); }
   else if (dm) { if (mk == 2) FWD7(1, 2); else if (mk == 1) FWD7(1, 1); else FWD7(1, 0); }
   else { if (mk == 2) FWD7(0, 2); else if (mk == 1) FWD7(0, 1); else FWD7(0, 0); }
 #undef FWD7R
@@ -1231,7 +1302,11 @@ int attn7_dq(AttnArgs& a, hipStream_t s) {
   const size_t lds = (size_t)4 * A7_TB + 2064 + (size_t)ntiles * 64 * 4;
   dim3 grid((a.Lq + 127) / 128, a.B * a.H);
 #define DQ7(D, M) hipLaunchKernelGGL((dq7_kernel<D, M>), grid, dim3(256), lds, s, a)
-  if (dm) { if (mk == 2) DQ7(1, 2); else if (mk == 1) DQ7(1, 1); else DQ7(1, 0); }
+  if (a.key_len && mk == 2) {
+    if (dm) hipLaunchKernelGGL((dq7_kernel<1, 2, true>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((dq7_kernel<0, 2, true>), grid, dim3(256), lds, s, a);
+  }
+  else if (dm) { if (mk == 2) DQ7(1, 2); else if (mk == 1) DQ7(1, 1); else DQ7(1, 0); }
   else { if (mk == 2) DQ7(0, 2); else if (mk == 1) DQ7(0, 1); else DQ7(0, 0); }
 #undef DQ7
   return (int)hipGetLastError();
@@ -1242,7 +1317,11 @@ int attn7_dkv(AttnArgs& a, hipStream_t s) {
   const size_t lds = (size_t)4 * A7_TB + 1024 + 2048;
   dim3 grid((a.Lk + 127) / 128, a.B * a.H);
 #define DKV7(D, M) hipLaunchKernelGGL((dkv7_kernel<D, M>), grid, dim3(256), lds, s, a)
-  if (dm) { if (a.key_keep) DKV7(1, true); else DKV7(1, false); }
+  if (a.key_len && a.key_keep) {
+    if (dm) hipLaunchKernelGGL((dkv7_kernel<1, true, true>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((dkv7_kernel<0, true, true>), grid, dim3(256), lds, s, a);
+  }
+  else if (dm) { if (a.key_keep) DKV7(1, true); else DKV7(1, false); }
   else { if (a.key_keep) DKV7(0, true); else DKV7(0, false); }
 #undef DKV7
   return (int)hipGetLastError();
@@ -1255,13 +1334,18 @@ int attn7_bwdf(AttnArgs& a, hipStream_t s) {
   const size_t lds = (size_t)16 * A7_TB + 1024 + 4096;
   dim3 grid(a.B * a.H);
 #define BWF7(D, M, P) hipLaunchKernelGGL((bwdf7_kernel<D, M, P>), grid, dim3(512), lds, s, a)
-  if (a.Lk <= 256) {
+#define BWF7X(D, P) hipLaunchKernelGGL((bwdf7_kernel<D, true, P, true>), grid, dim3(512), lds, s, a)
+  if (a.key_len && a.key_keep) {
+    if (a.Lk <= 256) { if (dm) BWF7X(1, 1); else BWF7X(0, 1); }
+    else { if (dm) BWF7X(1, 2); else BWF7X(0, 2); }
+  } else if (a.Lk <= 256) {
     if (dm) { if (a.key_keep) BWF7(1, true, 1); else BWF7(1, false, 1); }
     else { if (a.key_keep) BWF7(0, true, 1); else BWF7(0, false, 1); }
   } else {
     if (dm) { if (a.key_keep) BWF7(1, true, 2); else BWF7(1, false, 2); }
     else { if (a.key_keep) BWF7(0, true, 2); else BWF7(0, false, 2); }
   }
+#undef BWF7X
 #undef BWF7
   return (int)hipGetLastError();
 }

@@ -84,6 +84,8 @@ struct AttnArgs {
   float drop_scale;
   int bits_ready;  // host side only: dbits already holds this site's keep bits (fddm_attn_drop_bits)
   const uint64_t* seed_off;  // graph-replay seed offset (common.h eff_seed) or null
+  const int* key_len;        // [B] key extents (fddm_key_extent) or null: the 32x32x16 family's KX builds run batch
+                             // entry b's key tiles to max(1, ceil(key_len[b] / 64)) only (with key_keep)
 };
 
 __device__ __forceinline__ bool key_ok(const AttnArgs& a, int b, int key) {

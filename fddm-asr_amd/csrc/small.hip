@@ -80,6 +80,93 @@ __global__ void __launch_bounds__(256) rows_mean_kernel(const T* __restrict__ x,
   }
 }
 
+// ------------------------------------------------------------------------------------------ key-padding masks
+// key_len[b] = 1 + the largest k with key_keep[b][k] != 0 (0: none kept): the bound the length-bounded attention
+// kernels (attn7.hip, KX builds) run their key tiles to. One block per batch entry, 4 mask bytes per load where the
+// row is 4-byte aligned; the block maximum through an LDS atomic (integers: order-independent).
+__global__ void __launch_bounds__(256) key_extent_kernel(const unsigned char* __restrict__ keep, int Lk,
+                                                         int* __restrict__ key_len) {
+  __shared__ int ext;
+  if (threadIdx.x == 0) ext = 0;
+  __syncthreads();
+  const unsigned char* row = keep + (long)blockIdx.x * Lk;
+  int e = 0;
+  if ((((uintptr_t)row) & 3) == 0) {
+    const int n4 = Lk >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      const unsigned u = ((const unsigned*)row)[i];
+      if (u) e = 4 * i + 4 - (__builtin_clz(u) >> 3);  // the highest non-zero byte of the little-endian dword
+    }
+    for (int k = 4 * n4 + threadIdx.x; k < Lk; k += 256)
+      if (row[k]) e = k + 1;
+  } else {
+    for (int k = threadIdx.x; k < Lk; k += 256)
+      if (row[k]) e = k + 1;
+  }
+  if (e) atomicMax(&ext, e);
+  __syncthreads();
+  if (threadIdx.x == 0) key_len[blockIdx.x] = ext;
+}
+
+// out[b][j] = sum over kept rows s of x[b][s][j] / count, count = kept rows of entry b (clamp: at least 1). The
+// layout of rows_mean_kernel; rows that are padding are not loaded, each slice counts the kept rows it owns.
+template <typename T>
+__global__ void __launch_bounds__(256) rows_mean_masked_kernel(const T* __restrict__ x,
+                                                               const unsigned char* __restrict__ keep,
+                                                               float* __restrict__ out, long S, long d, int clamp) {
+  __shared__ float part[RM_SL][64 + 4];
+  __shared__ int cnt[RM_SL];
+  const int cg = threadIdx.x & 7, sl = threadIdx.x >> 3;
+  const long b = blockIdx.y, j0 = (long)blockIdx.x * 64 + cg * 8;
+  const unsigned char* kr = keep + b * S;
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+  int n = 0;
+  const bool vec = j0 + 8 <= d && (d % 8) == 0;
+  for (long s = sl; s < S; s += RM_SL) {
+    if (!kr[s]) continue;
+    ++n;
+    if (vec) {
+      float v[8];
+      rm_ld8<T>(x + (b * S + s) * d + j0, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += v[e];
+    } else {
+      for (int e = 0; e < 8; ++e)
+        if (j0 + e < d) acc[e] += ld<T>(x + (b * S + s) * d + j0 + e);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) part[sl][cg * 8 + e] = acc[e];
+  if (cg == 0) cnt[sl] = n;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int c = threadIdx.x;
+    const long j = (long)blockIdx.x * 64 + c;
+    if (j < d) {
+      float a = 0.f;
+      int m = 0;
+#pragma unroll
+      for (int q = 0; q < RM_SL; ++q) {
+        a += part[q][c];
+        m += cnt[q];
+      }
+      if (clamp && m < 1) m = 1;
+      out[b * d + j] = a / (float)m;  // unclamped and nothing kept: 0 / 0 = NaN, as the reference's masked mean
+    }
+  }
+}
+
+// rows of x [R][row_bytes] whose keep byte is 0 become zeros, 16 bytes per thread and store; kept rows are not touched
+__global__ void __launch_bounds__(256) rows_zero_masked_kernel(uint4* __restrict__ x,
+                                                               const unsigned char* __restrict__ keep, long R,
+                                                               long chunks) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= R * chunks) return;
+  if (!keep[i / chunks]) x[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // ------------------------------------------------------------------------------------------ time embedding
 // emb[b] = [sin(t f), cos(t f)], f_k = exp(-k * ln(max_steps) / (half - 1)) (SinusoidalTimeEmbedding.forward,
 // models/denoise_decoder.py:108-116: torch.linspace(log 1, log max_steps, half) * -1 then exp; odd d pads a 0)
@@ -464,6 +551,40 @@ FDDM_API int fddm_rows_mean(int dtype, const void* x, float* out, long B, long S
     hipLaunchKernelGGL(rows_mean_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)hs, (const bf16_t*)x, out, S, d);
   else
     hipLaunchKernelGGL(rows_mean_kernel<float>, g, dim3(256), 0, (hipStream_t)hs, (const float*)x, out, S, d);
+  return (int)hipGetLastError();
+}
+
+FDDM_API int fddm_key_extent(const unsigned char* key_keep, long B, long Lk, int* key_len, void* hs) {
+  if (B <= 0) return 0;
+  if (!key_keep || !key_len || Lk <= 0 || Lk > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(key_extent_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)hs, key_keep, (int)Lk, key_len);
+  return (int)hipGetLastError();
+}
+
+FDDM_API int fddm_rows_mean_masked(int dtype, const void* x, const unsigned char* key_keep, float* out, long B, long S,
+                                   long d, int clamp_count, void* hs) {
+  if (B <= 0 || d <= 0) return 0;
+  if (!key_keep || (((uintptr_t)x) & 15)) return (int)hipErrorInvalidValue;
+  dim3 g((unsigned)((d + 63) / 64), (unsigned)B);
+  if (dtype == FDDM_BF16)
+    hipLaunchKernelGGL(rows_mean_masked_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)hs, (const bf16_t*)x, key_keep,
+                       out, S, d, clamp_count);
+  else if (dtype == FDDM_F32)
+    hipLaunchKernelGGL(rows_mean_masked_kernel<float>, g, dim3(256), 0, (hipStream_t)hs, (const float*)x, key_keep, out,
+                       S, d, clamp_count);
+  else
+    return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
+FDDM_API int fddm_rows_zero_masked(int dtype, void* x, const unsigned char* key_keep, long R, long E, void* hs) {
+  if (R <= 0 || E <= 0) return 0;
+  if (dtype != FDDM_BF16 && dtype != FDDM_F32) return (int)hipErrorInvalidValue;
+  const long row_bytes = E * (dtype == FDDM_BF16 ? 2 : 4);
+  if (!key_keep || (((uintptr_t)x) & 15) || row_bytes % 16) return (int)hipErrorInvalidValue;
+  const long chunks = row_bytes / 16, n = R * chunks;
+  hipLaunchKernelGGL(rows_zero_masked_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hs,
+                     (uint4*)x, key_keep, R, chunks);
   return (int)hipGetLastError();
 }
 

@@ -205,7 +205,9 @@ class DecoderBlockFn(torch.autograd.Function):
     RoPE -> self-attn (kpm, dropout) -> +drop -> LN1 -> cross-attn -> +drop -> LN2 -> FiLM ->
     FF(GELU, dropout) -> +drop -> LN3.  Inputs: x (f32 [N,d], differentiable), xT (compute dtype copy),
     cT (cond, compute dtype [B*S,d], no grad), key_keep (u8 [B,L]), film scale/shift [B,d] (diff.),
-    then the 18 block parameters. Dropout sites use rng streams 6*layer + {1..6}."""
+    then the 18 block parameters. Dropout sites use rng streams 6*layer + {1..6}. meta[14:16] (optional): the
+    condition's key-padding mask (u8 [B,S]) and key extents for the cross-attention, kept in ctx.meta for the
+    backward."""
 
     @staticmethod
     def forward(ctx, x, xT, cT, key_keep, fscale, fshift, meta, *params):
@@ -253,8 +255,12 @@ class DecoderBlockFn(torch.autograd.Function):
             ops.linear(cT, W["ca"][d:], ca_b[d:], out_dtype=cd)      # (precomputed for all blocks in one GEMM)
         oc = torch.empty(N, d, device=dev, dtype=cd)
         lsec = torch.empty(B * H, L, device=dev, dtype=F32)
+        # the condition's key-padding mask (c_mask as u8 [B, S]) and its key extents (ops.key_extent), or None
+        c_keep = meta[14] if len(meta) > 14 else None
+        c_len = meta[15] if len(meta) > 15 else None
         fwd_c = lambda: ops.attn_fwd(qc, kvc, kvc[:, d:], oc, lsec, B, H, L, S, drop_p=p, seed=seed,  # noqa: E731
-                                     rng_stream=st + 3, dbits=bits_c, bits_ready=ready)
+                                     rng_stream=st + 3, dbits=bits_c, bits_ready=ready, key_keep=c_keep,
+                                     key_len=c_len)
         with rt.probe("decoder.cross_attn_fwd", replay=fwd_c):
             fwd_c()
         yc = ops.linear(oc, W["co"], co_b, out_dtype=cd)
@@ -344,8 +350,11 @@ class DecoderBlockFn(torch.autograd.Function):
         dqc = torch.empty(N, d, device=dev, dtype=cd)
         dkvc = torch.empty(B * S, 2 * d, device=dev, dtype=cd)
         bits_s, bits_c = ctx.bits
+        c_keep = ctx.meta[14] if len(ctx.meta) > 14 else None
+        c_len = ctx.meta[15] if len(ctx.meta) > 15 else None
         bwd_c = lambda: ops.attn_bwd(qc, kvc, kvc[:, d:], oc, doc, lsec, dqc, dkvc, dkvc[:, d:], B, H, L, S,  # noqa: E731
-                                     drop_p=p, seed=seed, rng_stream=st + 3, dbits=bits_c)
+                                     drop_p=p, seed=seed, rng_stream=st + 3, dbits=bits_c, key_keep=c_keep,
+                                     key_len=c_len)
         with rt.probe("decoder.cross_attn_bwd", replay=bwd_c):
             bwd_c()
         dw_jobs += [(dqc, x1T, gca_w[:d], gca_b[:d]), (dkvc, cT, gca_w[d:], gca_b[d:])]

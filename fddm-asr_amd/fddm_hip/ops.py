@@ -327,20 +327,44 @@ def attn_drop_bits(out, nsites, B, H, Lq, Lk, drop_p, seed, stream0, stream_step
     return out
 
 
+def _chk_key_len(key_len, key_keep, B, Lk):
+    _chk(key_keep is not None, "key_len comes with its key_keep mask")
+    _chk(key_keep.dtype == torch.uint8 and key_keep.is_contiguous() and key_keep.numel() == B * Lk,
+         "key_keep: contiguous uint8 [B, Lk]")
+    _chk(key_len.dtype == torch.int32 and key_len.is_contiguous() and key_len.numel() == B
+         and key_len.device == key_keep.device and key_len.is_cuda, "key_len: int32 [B] on the device")
+
+
+def key_extent(key_keep):
+    """key_keep [B, Lk] (uint8, contiguous; != 0 keeps) -> int32 [B]: 1 + the last kept key of each entry, 0 if none
+    (fddm_key_extent; one launch, no host sync). The key_len of attn_fwd / attn_bwd / attn_fwd_relgate_x."""
+    _chk(key_keep.dtype == torch.uint8 and key_keep.is_contiguous() and key_keep.dim() == 2 and key_keep.is_cuda,
+         "key_extent: contiguous uint8 [B, Lk] on the device")
+    B, Lk = key_keep.shape
+    _chk(Lk >= 1, "key_extent: at least one key")
+    out = torch.empty(B, device=key_keep.device, dtype=torch.int32)
+    call("fddm_key_extent", ptr(key_keep), B, Lk, ptr(out), stream())
+    return out
+
+
 def attn_fwd(q, k, v, out, lse, B, H, Lq, Lk, *, key_keep=None, gate=None, table=None, drop_p=0.0, seed=0,
-             rng_stream=0, scale=None, dbits=None, bits_ready=False):
+             rng_stream=0, scale=None, dbits=None, bits_ready=False, key_len=None):
     """q: [B*Lq, >=H*dh] row stride q.stride(0); k/v: [B*Lk, ...]; out [B*Lq, H*dh]; lse [B*H, Lq], dh =
     out.shape[1] // H. dbits (optional, drop_bits()): the dropout keep bits the backward reads; bits_ready: they
     were already written by attn_drop_bits (the forward only reads them), else the forward writes them.
     The kernels are built for head_dim 64; a smaller head_dim (the reference's nn.MultiheadAttention takes any
     d_model / nhead) runs them on zero-padded 64-wide head slots — the scores, the softmax, the dropout
-    element indices (b, h, query, key) and hence the RNG stream are those of the unpadded heads."""
+    element indices (b, h, query, key) and hence the RNG stream are those of the unpadded heads.
+    key_len (optional, key_extent(key_keep)): selects fddm_attn_fwd_kx, whose bf16 kernels stop each entry's key
+    tiles at its extent (same result as key_keep alone; fp32, Lk > 1024 and the padded small heads ignore it)."""
     _chk(q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1, "attention inputs need unit inner stride")
     _chk(q.dtype == k.dtype == v.dtype == out.dtype, "attention dtype mismatch")
     _chk(out.shape[1] % H == 0, "attention output width must be H * head_dim")
     _chk(table is None or gate is not None, "a relative-position bias table needs its gate")
     dh = out.shape[1] // H
     _chk(1 <= dh <= 64, f"head_dim {dh} > 64 is not built")
+    if key_len is not None:
+        _chk_key_len(key_len, key_keep, B, Lk)
     sc = 1.0 / math.sqrt(dh) if scale is None else scale
     if dh != 64:
         op = torch.empty(B * Lq, H * 64, device=out.device, dtype=out.dtype)
@@ -349,21 +373,34 @@ def attn_fwd(q, k, v, out, lse, B, H, Lq, Lk, *, key_keep=None, gate=None, table
                  scale=sc, dbits=dbits, bits_ready=bits_ready)
         _heads(out, B * Lq, H, dh).copy_(op.view(B * Lq, H, 64)[:, :, :dh])
         return out
+    if key_len is not None:
+        call("fddm_attn_fwd_kx", code(q), ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(out),
+             out.stride(0), ptr(lse), ptr(key_keep), ptr(key_len), ptr(gate), ptr(table), B, H, Lq, Lk, float(sc),
+             float(drop_p), seed, rng_stream, ptr(dbits), int(bool(bits_ready) and dbits is not None), stream())
+        return out
     call("fddm_attn_fwd", code(q), ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(out),
          out.stride(0), ptr(lse), ptr(key_keep), ptr(gate), ptr(table), B, H, Lq, Lk, float(sc), float(drop_p), seed,
          rng_stream, ptr(dbits), int(bool(bits_ready) and dbits is not None), stream())
     return out
 
 
-def attn_fwd_relgate_x(q, k, v, out, x, gw, gconst, table, B, H, L, scale=None):
+def attn_fwd_relgate_x(q, k, v, out, x, gw, gconst, table, B, H, L, scale=None, key_keep=None, key_len=None):
     """WavLM attention (bf16) with the gate computed in the kernel from the attention input x [B*L, H*64] (bf16, row
     stride x.stride(0)) and the folded gru_rel_pos_linear weights gw (130 floats: sum of weight rows 0-3, rows 4-7,
-    the two bias sums; models/wavlm.py)."""
+    the two bias sums; models/wavlm.py). key_keep [B, L] (uint8) with key_len = key_extent(key_keep): the key-padding
+    mask of a padded batch (fddm_attn_fwd_relgate_x_kx); both or neither."""
+    _chk((key_keep is None) == (key_len is None), "relgate attention: key_keep and key_len come together")
     _chk(q.dtype == k.dtype == v.dtype == out.dtype == x.dtype == torch.bfloat16, "relgate attention is bf16")
     _chk(x.stride(-1) == 1 and x.shape[1] >= H * 64 and x.data_ptr() % 16 == 0, "gate input layout")
     _chk(gw.dtype == torch.float32 and gw.numel() >= 130 and gw.is_contiguous() and gw.data_ptr() % 16 == 0,
          "folded gate weights")
     sc = 1.0 / math.sqrt(64) if scale is None else scale
+    if key_len is not None:
+        _chk_key_len(key_len, key_keep, B, L)
+        call("fddm_attn_fwd_relgate_x_kx", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(out),
+             out.stride(0), ptr(x), x.stride(0), ptr(gw), ptr(gconst), ptr(table), ptr(key_keep), ptr(key_len), B, H,
+             L, L, float(sc), stream())
+        return out
     call("fddm_attn_fwd_relgate_x", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(out),
          out.stride(0), ptr(x), x.stride(0), ptr(gw), ptr(gconst), ptr(table), B, H, L, L, float(sc), stream())
     return out
@@ -381,11 +418,14 @@ def attn_fwd_relgate(q, k, v, out, graw, gconst, table, B, H, L, scale=None):
 
 
 def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, *, key_keep=None, drop_p=0.0, seed=0, rng_stream=0,
-             dbits=None, scale=None):
-    """Gradients of attn_fwd (same layouts; head_dim = o.shape[1] // H, padded to 64 as in attn_fwd)."""
+             dbits=None, scale=None, key_len=None):
+    """Gradients of attn_fwd (same layouts; head_dim = o.shape[1] // H, padded to 64 as in attn_fwd). key_len as in
+    attn_fwd (fddm_attn_bwd_kx: dk / dv rows at or past an entry's extent are exact zeros)."""
     _chk(o.shape[1] % H == 0, "attention output width must be H * head_dim")
     dh = o.shape[1] // H
     _chk(1 <= dh <= 64, f"head_dim {dh} > 64 is not built")
+    if key_len is not None:
+        _chk_key_len(key_len, key_keep, B, Lk)
     sc = 1.0 / math.sqrt(dh) if scale is None else scale
     if dh != 64:
         rq, rk = B * Lq, B * Lk
@@ -401,6 +441,12 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, *, key_keep=None, dr
     # row-term workspace: delta = rowsum(dO O) and -LSE log2(e) per query, [2][B*H][Lq rounded up to 64] (the
     # 32x32x16 backward's layout; the other kernels use the first B*H*Lq floats)
     delta = torch.empty(int(lib().fddm_attn_bwd_ws_floats(B, H, Lq, Lk)), device=q.device, dtype=torch.float32)
+    if key_len is not None:
+        call("fddm_attn_bwd_kx", code(q), ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(o),
+             o.stride(0), ptr(do), do.stride(0), ptr(lse), ptr(dq), dq.stride(0), ptr(dk), dk.stride(0), ptr(dv),
+             dv.stride(0), ptr(delta), ptr(key_keep), ptr(key_len), B, H, Lq, Lk, float(sc), float(drop_p), seed,
+             rng_stream, ptr(dbits), stream())
+        return
     call("fddm_attn_bwd", code(q), ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(o),
          o.stride(0), ptr(do), do.stride(0), ptr(lse), ptr(dq), dq.stride(0), ptr(dk), dk.stride(0), ptr(dv),
          dv.stride(0), ptr(delta), ptr(key_keep), B, H, Lq, Lk, float(sc), float(drop_p), seed, rng_stream,
@@ -671,6 +717,31 @@ def rows_mean(x3d):
     out = torch.empty(B, d, device=x3d.device, dtype=torch.float32)
     call("fddm_rows_mean", code(x3d), ptr(x3d), ptr(out), B, S, d, stream())
     return out
+
+
+def rows_mean_masked(x3d, key_keep, clamp=False):
+    """[B, S, d] (f32 / bf16, contiguous), key_keep [B, S] uint8 -> f32 [B, d]: the sum over kept rows divided by the
+    kept count (clamp: by at least 1 — AcousticEncoder pooling; unclamped, an entry with nothing kept is NaN, as the
+    reference decoder's masked mean)."""
+    B, S, d = x3d.shape
+    _chk(x3d.is_contiguous() and x3d.data_ptr() % 16 == 0, "rows_mean_masked: contiguous 16-byte-aligned input")
+    _chk(key_keep.dtype == torch.uint8 and key_keep.is_contiguous() and key_keep.numel() == B * S
+         and key_keep.device == x3d.device, "rows_mean_masked: contiguous uint8 [B, S] mask")
+    out = torch.empty(B, d, device=x3d.device, dtype=torch.float32)
+    call("fddm_rows_mean_masked", code(x3d), ptr(x3d), ptr(key_keep), ptr(out), B, S, d, int(bool(clamp)), stream())
+    return out
+
+
+def rows_zero_masked(x2d, key_keep):
+    """Rows of x2d [R, E] (f32 / bf16, contiguous; in place) whose key_keep byte (uint8, R of them) is 0 become
+    zeros."""
+    R, E = x2d.shape
+    _chk(x2d.is_contiguous() and x2d.data_ptr() % 16 == 0 and (E * x2d.element_size()) % 16 == 0,
+         "rows_zero_masked: contiguous rows of a multiple of 16 bytes")
+    _chk(key_keep.dtype == torch.uint8 and key_keep.is_contiguous() and key_keep.numel() == R
+         and key_keep.device == x2d.device, "rows_zero_masked: contiguous uint8 mask, one byte per row")
+    call("fddm_rows_zero_masked", code(x2d), ptr(x2d), ptr(key_keep), R, E, stream())
+    return x2d
 
 
 def time_embed(t, d, max_steps):

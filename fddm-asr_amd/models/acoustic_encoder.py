@@ -48,12 +48,26 @@ class AcousticEncoder(nn.Module):
 
     def forward(self, waveforms: torch.Tensor, lengths: Optional[torch.Tensor] = None
                 ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
-        if lengths is not None:
-            raise NotImplementedError("lengths-masked encoding is not on the train step (train.py:349)")
+        if lengths is None:
+            with torch.no_grad():
+                feats = self.project(self.backbone.forward_hidden(waveforms))
+            pooled = feats.float().mean(dim=1) if self.pooling == "mean" else None
+            return feats, None, pooled
+        # reference acoustic_encoder.py:92-128
         with torch.no_grad():
-            feats = self.project(self.backbone.forward_hidden(waveforms))
-        pooled = feats.float().mean(dim=1) if self.pooling == "mean" else None
-        return feats, None, pooled
+            lengths = lengths.to(waveforms.device)
+            attention_mask = self._make_mask(lengths, waveforms.shape[1])             # (:96) ids < lengths
+            feats = self.project(self.backbone.forward_hidden(waveforms, attention_mask))
+            S = feats.shape[1]
+            # (:73-82, :114-117) the reference's own frame count ceil(len / 320) clamped to S — slightly longer than the
+            # backbone's (HF floors through the conv stack): the returned mask keeps a few frames the backbone treated
+            # as padding. Kept as the reference has it; the decoder sees exactly this mask.
+            feat_mask = self._make_mask(torch.clamp((lengths + 319) // 320, max=S), S)
+            pooled = None
+            if self.pooling == "mean":                                                 # (:125-126) count clamped to >= 1
+                keep = feat_mask.contiguous().view(torch.uint8)
+                pooled = ops.rows_mean_masked(feats.contiguous(), keep, clamp=True)
+        return feats, feat_mask, pooled
 
     @torch.no_grad()
     def project(self, h: torch.Tensor) -> torch.Tensor:

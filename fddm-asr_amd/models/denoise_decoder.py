@@ -23,7 +23,9 @@ from fddm_hip import runtime as rt
 from fddm_hip.ops import attn_drop_bits as ops_attn_drop_bits
 from fddm_hip.ops import drop_words
 from fddm_hip.ops import linear as ops_linear
+from fddm_hip.ops import key_extent as ops_key_extent
 from fddm_hip.ops import rows_mean as ops_rows_mean
+from fddm_hip.ops import rows_mean_masked as ops_rows_mean_masked
 
 
 class RoPEEmbedding(nn.Module):
@@ -125,15 +127,16 @@ class DecoderBlock(nn.Module):
                 self.norm2.bias, self.norm3.weight, self.norm3.bias)
 
     def run(self, x, xT, cT, key_keep, film, B, L, S, layer, seed, cos, sin, kv=None, bits=None, xr=None,
-            handoff=None):
+            handoff=None, c_keep=None, c_len=None):
         """film = (scale, shift, (dscale, dshift) accumulators or None) from DenoisingTransformerDecoder's
         conditioning Function; kv = this block's precomputed cross-attention K|V [B*S, 2d] (strided view) or None;
         bits = (self, cross) attention-dropout keep-bit words already written for this block, or None;
         xr = rope(x) already written by the previous block's LN3, or None; handoff = a dict in which this block's LN3
-        leaves rope(its output) under "xr" for the next block (bf16), or None."""
+        leaves rope(its output) under "xr" for the next block (bf16), or None; c_keep / c_len = the condition's
+        key-padding mask (u8 [B, S]) and its key extents for the cross-attention (:169-174), or None."""
         fscale, fshift, gfilm = film
         p = self.p if self.training else 0.0
-        meta = (B, L, S, self.nhead, layer, p, seed, cos, sin, gfilm, kv, bits, xr, handoff)
+        meta = (B, L, S, self.nhead, layer, p, seed, cos, sin, gfilm, kv, bits, xr, handoff, c_keep, c_len)
         return FN.DecoderBlockFn.apply(x, xT, cT, key_keep, fscale, fshift, meta, *self.block_params())
 
 
@@ -160,16 +163,25 @@ class DenoisingTransformerDecoder(nn.Module):
 
     def forward(self, xt: torch.Tensor, t: torch.Tensor, cond: torch.Tensor, x_mask: Optional[torch.Tensor] = None,
                 c_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if c_mask is not None:
-            raise NotImplementedError("c_mask is never set on the train step (AcousticEncoder lengths=None)")
         B, L = xt.shape
         S = cond.shape[1]
         dev = xt.device
         cd = rt.compute_dtype()
         # conditioning (:272-274 time bias, :185 pooled condition -> FiLM of every block) in one Function
+        c_keep = c_len = None
         with torch.no_grad():
             cc = cond.detach()
-            pooled = ops_rows_mean(cc if cc.is_contiguous() else cc.contiguous())   # (:185) mean over S, f32
+            cc = cc if cc.is_contiguous() else cc.contiguous()
+            if c_mask is None:
+                pooled = ops_rows_mean(cc)                                          # (:185) mean over S, f32
+            else:
+                # (:173, :181-183) the condition's key-padding mask for every block's cross-attention, its key extents
+                # (once per forward, no host sync) and the masked pooled mean (count not clamped, as the reference)
+                c_keep = c_mask.to(dev)
+                c_keep = c_keep.contiguous().view(torch.uint8) if c_keep.dtype == torch.bool else \
+                    (c_keep != 0).contiguous().view(torch.uint8)
+                c_len = ops_key_extent(c_keep)
+                pooled = ops_rows_mean_masked(cc, c_keep, clamp=False)
         nb = len(self.blocks)
         gbuf = torch.zeros(2 * nb, B, self.d_model, device=dev, dtype=torch.float32)
         te = self.time_emb
@@ -199,7 +211,8 @@ class DenoisingTransformerDecoder(nn.Module):
             kv = None if kv_all is None else kv_all[:, 2 * self.d_model * i: 2 * self.d_model * (i + 1)]
             bi = None if bits is None else (bits[0][i], bits[1][i])
             handoff = {} if i + 1 < len(self.blocks) else None
-            x, xT = blk.run(x, xT, cT, key_keep, film, B, L, S, i, seed, cos, sin, kv, bi, xr, handoff)
+            x, xT = blk.run(x, xT, cT, key_keep, film, B, L, S, i, seed, cos, sin, kv, bi, xr, handoff, c_keep,
+                            c_len)
             xr = None if handoff is None else handoff.get("xr")
         logits = FN.HeadFn.apply(x, xT, self.head.weight, self.head.bias)           # (:286)
         return logits.view(B, L, -1)

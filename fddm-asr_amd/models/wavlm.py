@@ -232,8 +232,24 @@ class WavLMModel(nn.Module):
         return out
 
     @torch.no_grad()
-    def stage_rest(self, h: torch.Tensor) -> torch.Tensor:
-        """conv layers 2..6, feature projection, positional conv, 12 transformer layers -> [B, S, E]."""
+    def feature_mask(self, attention_mask: torch.Tensor, S: int) -> torch.Tensor:
+        """The frame-level mask [B, S] (bool) of a sample-level attention_mask [B, T], as HF
+        _get_feature_vector_attention_mask (modeling_wavlm.py:654-672): the kept-sample count through every conv
+        layer's floor((n - k) / s) + 1 (:633-652, integer arithmetic on the device), frames 0 .. length - 1 kept. A
+        length of 0 keeps every frame there (HF sets index -1 before its reversed cumsum); so does this."""
+        n = attention_mask.to(torch.int64).sum(-1)
+        for k, s in zip(self.config.conv_kernel, self.config.conv_stride):
+            n = torch.div(n - k, s, rounding_mode="floor") + 1
+        last = n - 1
+        last = torch.where(last < 0, last + S, last)
+        return torch.arange(S, device=n.device).unsqueeze(0) <= last.unsqueeze(1)
+
+    @torch.no_grad()
+    def stage_rest(self, h: torch.Tensor, feat_keep: torch.Tensor | None = None) -> torch.Tensor:
+        """conv layers 2..6, feature projection, positional conv, 12 transformer layers -> [B, S, E].
+        feat_keep (uint8 [B, S], != 0 keeps; None: no padding): HF's attention_mask path — padded frames are zeroed
+        after the feature projection and before the positional conv (modeling_wavlm.py:399-402) and are no keys in any
+        layer's attention (:198); their output rows are whatever the layers leave there (HF does not zero them)."""
         c = self.config
         cd = rt.compute_dtype()
         P = self._prepared(cd)
@@ -248,6 +264,10 @@ class WavLMModel(nn.Module):
         hn = torch.empty_like(h2)
         ops.ln_fwd(h2, None, P["fp_ln"][0], P["fp_ln"][1], out_t=hn, eps=eps)
         x = ops.linear(hn, P["fp"][0], P["fp"][1], out_dtype=cd)
+        key_len = None
+        if feat_keep is not None:
+            ops.rows_zero_masked(x, feat_keep)
+            key_len = ops.key_extent(feat_keep)      # one launch, no host sync; every layer's attention reads it
         # positional conv embedding + LN (HF:37-90, 399-407)
         G = c.num_conv_pos_embedding_groups
         Cg = E // G
@@ -267,12 +287,14 @@ class WavLMModel(nn.Module):
             qkv = ops.linear(x, Lp["qkv"], Lp["bqkv"], out_dtype=cd)
             o = torch.empty(B * S, E, device=dev, dtype=cd)
             if cd == torch.bfloat16 and GATE_MODE == "x":
-                ops.attn_fwd_relgate_x(qkv, qkv[:, E:], qkv[:, 2 * E:], o, x, Lp["gw"], Lp["gru"][2], table, B, H, S)
-            elif cd == torch.bfloat16 and GATE_MODE == "cols":
+                ops.attn_fwd_relgate_x(qkv, qkv[:, E:], qkv[:, 2 * E:], o, x, Lp["gw"], Lp["gru"][2], table, B, H, S,
+                                       key_keep=feat_keep, key_len=key_len)
+            elif cd == torch.bfloat16 and GATE_MODE == "cols" and feat_keep is None:
                 ops.attn_fwd_relgate(qkv, qkv[:, E:], qkv[:, 2 * E:], o, qkv[:, 3 * E:], Lp["gru"][2], table, B, H, S)
-            else:
+            else:   # fp32; or a masked batch under the "cols" / "separate" gate modes: the general entry
                 gate = ops.wavlm_gate(x, Lp["gru"][0], Lp["gru"][1], Lp["gru"][2], B, S, H)
-                ops.attn_fwd(qkv, qkv[:, E:], qkv[:, 2 * E:], o, None, B, H, S, S, gate=gate, table=table)
+                ops.attn_fwd(qkv, qkv[:, E:], qkv[:, 2 * E:], o, None, B, H, S, S, gate=gate, table=table,
+                             key_keep=feat_keep, key_len=key_len)
             y = ops.linear(o, Lp["o"][0], Lp["o"][1], out_dtype=cd)
             x1 = torch.empty_like(x)
             ops.ln_fwd(x, y, Lp["ln1"][0], Lp["ln1"][1], out_t=x1, eps=eps)
@@ -283,14 +305,18 @@ class WavLMModel(nn.Module):
         return x.view(B, S, E)
 
     @torch.no_grad()
-    def forward_hidden(self, wave: torch.Tensor) -> torch.Tensor:
-        """last_hidden_state [B, S, E] in the compute dtype (eval mode, attention_mask=None)."""
-        return self.stage_rest(self.stage_conv1(self.stage_conv0(wave)))
+    def forward_hidden(self, wave: torch.Tensor, attention_mask: torch.Tensor | None = None) -> torch.Tensor:
+        """last_hidden_state [B, S, E] in the compute dtype (eval mode). attention_mask [B, T] (sample level, != 0
+        keeps, right-padded) as HF WavLMModel.forward (modeling_wavlm.py:1053-1073): the conv feature extractor runs
+        on the whole padded waveform unmasked; the mask takes effect from the feature projection on (stage_rest)."""
+        h = self.stage_conv1(self.stage_conv0(wave))
+        if attention_mask is None:
+            return self.stage_rest(h)
+        keep = self.feature_mask(attention_mask, self.frames(wave.shape[1]))
+        return self.stage_rest(h, keep.contiguous().view(torch.uint8))
 
     def forward(self, input_values, attention_mask=None, output_hidden_states=False, **kw):
-        if attention_mask is not None:
-            raise NotImplementedError("attention_mask is never passed on the train step (lengths=None)")
-        return SimpleNamespace(last_hidden_state=self.forward_hidden(input_values))
+        return SimpleNamespace(last_hidden_state=self.forward_hidden(input_values, attention_mask))
 
     # ------------------------------------------------------------------ loading
     random_init = True      # False once weights were loaded from a checkpoint

@@ -37,8 +37,8 @@ class ModelAdapter:
         self.decoder = decoder
 
     @torch.no_grad()
-    def predict_x0_logits(self, x_t_idx: Tensor, t: Tensor, cond_c: Tensor) -> Tensor:
-        return self.decoder(x_t_idx, t, cond_c)
+    def predict_x0_logits(self, x_t_idx: Tensor, t: Tensor, cond_c: Tensor, c_mask: Optional[Tensor] = None) -> Tensor:
+        return self.decoder(x_t_idx, t, cond_c, c_mask=c_mask)
 
 
 class DiffusionJumpySampler:
@@ -115,10 +115,14 @@ class DiffusionJumpySampler:
             t -= delta
         return plan
 
-    def _step(self, x: Tensor, t_scalar: int, delta: int, cond_c: Tensor, coef: Tensor):
+    def _step(self, x: Tensor, t_scalar: int, delta: int, cond_c: Tensor, coef: Tensor,
+              c_mask: Optional[Tensor] = None):
         B, L = x.shape
         t_tensor = torch.full((B,), t_scalar, device=x.device, dtype=torch.long)
-        logits = self.model.predict_x0_logits(x, t_tensor, cond_c)
+        if c_mask is None:
+            logits = self.model.predict_x0_logits(x, t_tensor, cond_c)
+        else:
+            logits = self.model.predict_x0_logits(x, t_tensor, cond_c, c_mask)
         z = logits.reshape(B * L, -1)
         if z.dtype != torch.float32 or z.stride(-1) != 1:
             z = z.float().contiguous()
@@ -127,58 +131,69 @@ class DiffusionJumpySampler:
                            seed=seed, rng_stream=7)
         return nx.view(B, L), x0h.view(B, L), logits
 
-    def _run(self, x: Tensor, cond_c: Tensor, plan):
+    def _run(self, x: Tensor, cond_c: Tensor, plan, c_mask: Optional[Tensor] = None):
         x0h = logits = None
         for t, delta, coef in plan:
-            x, x0h, logits = self._step(x, t, delta, cond_c, coef)
+            x, x0h, logits = self._step(x, t, delta, cond_c, coef, c_mask)
         return x, x0h, logits
 
     @torch.no_grad()
     def _jump_once(self, x_t_idx: Tensor, t_scalar: int, delta: int, cond_c: Tensor,
-                   seq_len: int) -> Tuple[Tensor, Tensor]:
+                   seq_len: int, c_mask: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """jumpy_sampler.py:167-215: returns (x_{t-Δ} [B, L], p_x0 [B, L, K])."""
         coef = self._coef(t_scalar, delta, x_t_idx.shape[0])
-        nx, _, logits = self._step(x_t_idx, t_scalar, delta, cond_c, coef)
+        nx, _, logits = self._step(x_t_idx, t_scalar, delta, cond_c, coef, c_mask)
         return nx, F.softmax(logits.float(), dim=-1)
 
     # -------------------------------------------------------------------------- public API
     @torch.no_grad()
     def sample(self, cond_c: Tensor, seq_len: int, init: Literal["uniform", "random"] = "uniform",
-               graph: bool = False, return_probs: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+               graph: bool = False, return_probs: bool = True,
+               c_mask: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
         """jumpy_sampler.py:238-293: x_T ~ U{0..K-1}, jump by Δ = min(r, t) until t = 0; returns
         (argmax x̂0 of the last jump [B, L], p_x0_last [B, L, K] or None when return_probs=False).
-        graph=True replays the whole loop from a captured HIP graph (captured on first use per shape)."""
+        graph=True replays the whole loop from a captured HIP graph (captured on first use per shape).
+        c_mask [B, S] (True keeps; the encoder's frame mask of a padded batch) goes to every decoder call; the graph
+        path keeps one graph per (shape, mask present) and copies the mask into a static buffer like cond_c."""
         B = cond_c.size(0)
         device = cond_c.device
         x_T = torch.randint(low=0, high=self.K, size=(B, seq_len), device=device)
         if graph:
-            x0, logits = self._sample_graph(x_T, cond_c)
+            x0, logits = self._sample_graph(x_T, cond_c, c_mask)
         else:
-            _, x0, logits = self._run(x_T, cond_c, self._plan(B))
+            _, x0, logits = self._run(x_T, cond_c, self._plan(B), c_mask)
         if not return_probs:
             return x0, None
         return x0, F.softmax(logits.float(), dim=-1)
 
-    def _sample_graph(self, x_T: Tensor, cond_c: Tensor):
+    def _sample_graph(self, x_T: Tensor, cond_c: Tensor, c_mask: Optional[Tensor] = None):
         B, L = x_T.shape
-        key = (B, L, tuple(cond_c.shape[1:]), cond_c.dtype, self.T_infer, self.r, self._mode(), self.temperature)
+        key = (B, L, tuple(cond_c.shape[1:]), cond_c.dtype, self.T_infer, self.r, self._mode(), self.temperature,
+               c_mask is not None)
+        if c_mask is not None:
+            c_mask = c_mask.to(device=cond_c.device, dtype=torch.bool)
         ent = self._graphs.get(key)
         if ent is None:
             plan = self._plan(B)
             sx, sc = x_T.clone(), cond_c.detach().clone()
+            sm = None if c_mask is None else c_mask.clone()
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):       # warm-up: weight caches, RoPE tables, library handles
-                self._run(sx, sc, plan)
+                self._run(sx, sc, plan, sm)
             torch.cuda.current_stream().wait_stream(s)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                _, x0, logits = self._run(sx, sc, plan)
-            ent = (g, sx, sc, x0, logits)
+                _, x0, logits = self._run(sx, sc, plan, sm)
+            # the captured launches read the plan's coefficient tensors by address: the entry keeps them alive (freed,
+            # their blocks would be handed to later allocations and a replay would jump with whatever those hold)
+            ent = (g, sx, sc, x0, logits, sm, plan)
             self._graphs[key] = ent
-        g, sx, sc, x0, logits = ent
+        g, sx, sc, x0, logits, sm, _plan = ent
         sx.copy_(x_T)
         sc.copy_(cond_c)
+        if sm is not None:
+            sm.copy_(c_mask)
         g.replay()
         return x0.clone(), logits
 

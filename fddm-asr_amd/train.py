@@ -121,7 +121,8 @@ def cu_caps(dev) -> dict:
 
 
 def _encoded(encoder, loader, device, optimizer):
-    """Yields (c, c_mask, x0) per batch. The encoder is frozen (eval mode, none of its parameters in the
+    """Yields (c, c_mask, x0) per batch; a batch's third element, if present, is the utterances' sample counts
+    (`lengths` of AcousticEncoder.forward: c_mask is then the encoder's frame mask, else None). The encoder is frozen (eval mode, none of its parameters in the
     optimizer; train.py:543), so its output for batch i+1 does not depend on step i: on a GPU it is computed
     on a second HIP stream, enqueued before step i's decoder work, and the two run concurrently (the persistent
     encoder GEMMs fill the CUs the decoder's small, latency-bound launches leave idle). Every batch is still
@@ -133,10 +134,13 @@ def _encoded(encoder, loader, device, optimizer):
         bb = getattr(encoder, "backbone", None)
         if bb is not None and getattr(bb, "conv_cus", 0):
             bb.conv_cus = bb.conv_cus_rest = 0  # nothing runs beside it: the conv GEMMs get the whole chip
-        for wave, x0 in loader:
+        for wave, x0, *rest in loader:
             wave = wave.to(device, non_blocking=True)
             x0 = x0.to(device, non_blocking=True)
-            c, c_mask, _ = encoder(wave)
+            if rest and rest[0] is not None:
+                c, c_mask, _ = encoder(wave, rest[0].to(device, non_blocking=True))
+            else:
+                c, c_mask, _ = encoder(wave)
             yield c, c_mask, x0
         return
     main = torch.cuda.current_stream(dev)
@@ -160,14 +164,17 @@ def _encoded(encoder, loader, device, optimizer):
     nbatch = [0]
 
     def launch(batch):
-        wave, x0 = batch
+        wave, x0, *rest = batch
         wave = wave.to(device, non_blocking=True)
         x0 = x0.to(device, non_blocking=True)
+        lengths = rest[0].to(device, non_blocking=True) if rest and rest[0] is not None else None
         side.wait_stream(main)                  # inputs (and memory the main stream freed) are ready
         prev = _fddm_lib().fddm_gemm_persistent_cap(enc_cus)
         try:
             with torch.cuda.stream(side):
-                if graphs is not None:
+                if lengths is not None:         # the graph-replayed encoder takes batches without lengths only
+                    c, c_mask, _ = encoder(wave, lengths)
+                elif graphs is not None:
                     c, c_mask = graphs.run(wave, nbatch[0] % 2, enc_cus), None
                 else:
                     c, c_mask, _ = encoder(wave)
@@ -178,6 +185,8 @@ def _encoded(encoder, loader, device, optimizer):
             ev = torch.cuda.Event()
             ev.record(side)
         wave.record_stream(side)
+        if lengths is not None:
+            lengths.record_stream(side)
         return c, c_mask, x0, ev
 
     it = iter(loader)

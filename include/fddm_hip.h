@@ -150,6 +150,36 @@ int fddm_attn_bwd(int dtype, const void* Q, long sq, const void* K, long sk, con
                   float scale, float drop_p, unsigned long long seed, unsigned long long stream,
                   const unsigned long long* drop_bits, void* hip_stream);
 
+/* ---- length-bounded attention (variable-length audio: a right-padded batch leaves whole 64-key tiles dead).
+ *      The argument lists of fddm_attn_fwd / fddm_attn_bwd / fddm_attn_fwd_relgate_x plus key_len [B] (int, device;
+ *      fddm_key_extent of key_keep, which stays required): for bf16 and Lk <= 1024 the 32x32x16 family's
+ *      length-bounded builds (csrc/attn7.hip KX: fwd7, its WavLM bias build, bwdf7, dq7, dkv7 — never fwd8) run
+ *      batch entry b's key-tile loop over max(1, ceil(key_len[b] / 64)) tiles instead of ceil(Lk / 64); the mask of
+ *      the last live tile is key_keep AND k < key_len[b]; key-owned workgroups / passes / waves past the live tiles
+ *      store zeros to their dK / dV rows and do no other work; keep-bit words of skipped tiles are not read (producer
+ *      and layout unchanged). fp32, Lk > 1024 and fddm_attn_set_kernels(1) ignore key_len and run the key_keep path:
+ *      same result, nothing skipped. Entries with at least one kept key get the bits of the key_keep path. A fully
+ *      masked entry (key_len[b] == 0) keeps its NaN output / LSE rows (no tile runs for it in the forward and dQ
+ *      kernels); in the backward its dK / dV rows are NaN in the first 64 (fused backward) or 128 (dK / dV kernel of
+ *      the split pair) keys and zeros past them, where the key_keep path leaves NaN in all of them. key_len[b] must cover every kept key of entry b (it does when it comes from
+ *      fddm_key_extent); a smaller value masks the keys at and past it.
+ *      Cross-attention to a padded acoustic condition (reference models/denoise_decoder.py:169-176,
+ *      key_padding_mask = ~c_mask) and WavLM's masked self-attention (HF modeling_wavlm.py:569-596). */
+int fddm_attn_fwd_kx(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv, void* O,
+                     long so, float* lse, const unsigned char* key_keep, const int* key_len, const float* gate,
+                     const float* table, int B, int H, int Lq, int Lk, float scale, float drop_p,
+                     unsigned long long seed, unsigned long long stream, unsigned long long* drop_bits,
+                     int drop_bits_ready, void* hip_stream);
+int fddm_attn_bwd_kx(int dtype, const void* Q, long sq, const void* K, long sk, const void* V, long sv, const void* O,
+                     long so, const void* dO, long sdo, const float* lse, void* dQ, long sdq, void* dK, long sdk,
+                     void* dV, long sdv, float* delta_ws, const unsigned char* key_keep, const int* key_len, int B,
+                     int H, int Lq, int Lk, float scale, float drop_p, unsigned long long seed,
+                     unsigned long long stream, const unsigned long long* drop_bits, void* hip_stream);
+int fddm_attn_fwd_relgate_x_kx(const void* Q, long sq, const void* K, long sk, const void* V, long sv, void* O,
+                               long so, const void* x, long sx, const float* gw, const float* gconst,
+                               const float* table, const unsigned char* key_keep, const int* key_len, int B, int H,
+                               int Lq, int Lk, float scale, void* hip_stream);
+
 /* ---- residual + dropout + LayerNorm (+FiLM). models/denoise_decoder.py:87-89,165-191;
  *      HF modeling_wavlm.py:102,313-317,405. rope_out (optional, bf16; the decoder's LN3 only: f32 x, bf16 y and
  *      output, no FiLM): also writes RoPE(out) with the [rope_L][d] cos / sin tables, as fddm_rope_fwd would
@@ -304,6 +334,20 @@ int fddm_small_dw(int njobs, const float* const* dy, const long* lddy, const flo
                   float* const* dW, float* const* db, const long* N, const long* K, long R, void* hip_stream);
 int fddm_kl_reduce(const float* kl_tok, const unsigned char* mask, float* w, float* loss, long B, long L,
                    void* hip_stream);
+
+/* ---- key-padding masks of variable-length audio (key_keep [B][S] u8, != 0 keeps).
+ *      key_extent: key_len[b] = 1 + the largest k with key_keep[b][k] != 0, 0 if none — one launch, no host sync,
+ *        any mask (a right-padded one gets its true length; holes stay holes: the byte mask still applies inside the
+ *        bound). The bound of fddm_attn_fwd_kx / _bwd_kx.
+ *      rows_mean_masked: out[b][j] = sum over kept s of x[b][s][j] / count_b, f32 sums; clamp_count != 0 clamps the
+ *        count to >= 1 (AcousticEncoder pooling, reference models/acoustic_encoder.py:125-126), 0 leaves it (the
+ *        decoder's FiLM condition, models/denoise_decoder.py:181-183: nothing kept gives NaN as there).
+ *      rows_zero_masked: rows of x [R][E] (in place) whose key_keep byte is 0 become zeros, 16-byte stores (row bytes
+ *        a multiple of 16) — WavLM's padded frames after the feature projection (HF modeling_wavlm.py:399-402). */
+int fddm_key_extent(const unsigned char* key_keep, long B, long Lk, int* key_len, void* hip_stream);
+int fddm_rows_mean_masked(int dtype, const void* x, const unsigned char* key_keep, float* out, long B, long S, long d,
+                          int clamp_count, void* hip_stream);
+int fddm_rows_zero_masked(int dtype, void* x, const unsigned char* key_keep, long R, long E, void* hip_stream);
 
 /* ---- jumpy sampler denoise step (sampler/jumpy_sampler.py:167-215 + q_posterior_multi_step,
  *      fddm/sched/diffusion_scheduler.py:106-208): x_next = argmax (or a tempered draw) of the
