@@ -2398,7 +2398,8 @@ __global__ void __launch_bounds__(1024, 1) bwd3s_kernel(AttnArgs a) {
 //           32-query chains per wave on 32x32x16 MFMAs; keep bits from the producer); Lk > 1024: fwd2.
 //  backward decoder, recorded bits or no dropout: Lq <= 256 and Lk <= 512: bwdf7 (attn7.hip, one fused launch per
 //           (b, h), one pass per 256 keys); other Lk <= 1024: dq7 + dkv7; longer or rehashed:
-//           dq2 + dkv2. Under fddm_attn_set_kernels(1) the round-4 kernels: bwd3s (Lq == Lk <= 256), dq4 + dkv4.
+//           dq2 + dkv2 (the dK / dV launch is chosen on its own: with Lk > 1024, Lq <= 1024 and no rehash it is dkv4).
+//           Under fddm_attn_set_kernels(1) the round-4 kernels: bwd3s (Lq == Lk <= 256), dq4 + dkv4.
 // fddm_attn_set_kernels (tests / tools only): 1 selects the round-4 16x16x32 kernels (fwd6 / dq4 / dkv4 / bwd3s)
 // where the 32x32x16 family (attn7.hip) would run; 0 (default) the 32x32x16 family with the two-chain forward fwd8
 // (attn8.hip); 2 the same without the fused backward (dq7 + dkv7 at every Lk); 3 the default with fwd7 as the forward;
@@ -2409,6 +2410,21 @@ static int g_attn_v6 = 0;
                             // (b, h) walks every 64-query tile, measured slower than dq7 + dkv7 at Lq 512)
 #endif
 static bool attn7_enabled() { return g_attn_v6 != 1; }
+
+// The kernels the most recent forward / backward call launched (fddm_attn_last_path; the layout of the two words is in
+// attn_common.h): written by the launch wrappers here and in attn7.hip / attn8.hip, read by tests. No device code.
+static int g_last_fwd = AF_NONE, g_last_bwd = AB_NONE;
+void attn_note_fwd(int kernel, int dm, int mk, bool kx, bool rel) {
+  g_last_fwd = kernel | (dm << 4) | (mk << 6) | ((int)kx << 8) | ((int)rel << 9);
+}
+void attn_note_bwd(int kernel, int dm, int mk, int np, bool kx) {
+  g_last_bwd = kernel | (dm << 4) | (mk << 6) | (np << 9) | ((int)kx << 11);
+}
+void attn_note_dkv(int kernel, int dm, bool mask, bool kx) {
+  // the two launches of a backward share DM and KX by construction; a disagreement shows as AB_DISAGREE
+  const bool same = ((g_last_bwd >> 4) & 3) == dm && (((g_last_bwd >> 11) & 1) != 0) == kx;
+  g_last_bwd |= ((same ? kernel : (int)AB_DISAGREE) << 12) | ((int)mask << 8);
+}
 // compute units of the current device (cached; one process drives one GPU)
 static long attn_cu_count() {
   static int n = 0;
@@ -2440,6 +2456,7 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
         dim3 grid5((a.Lq + 127) / 128, a.B * a.H);
         if (mask) hipLaunchKernelGGL((fwd5_kernel<true, 2, 2>), grid5, dim3(256), lds5, s, a);
         else hipLaunchKernelGGL((fwd5_kernel<false, 2, 2>), grid5, dim3(256), lds5, s, a);
+        attn_note_fwd(AF_FWD5, 0, mask, false, true);
         return (int)hipGetLastError();
       }
       if (a.Lk <= 1024) {
@@ -2473,6 +2490,7 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
         else FWD6M(0);
 #undef FWD6M
 #undef FWD6
+        attn_note_fwd(AF_FWD6, dm, mk, false, false);
         return (int)hipGetLastError();
       }
       dim3 grid((a.Lq + 127) / 128, a.B * a.H);
@@ -2480,6 +2498,7 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
       if (drop) { if (mask) FWD2(true, true); else FWD2(true, false); }
       else { if (mask) FWD2(false, true); else FWD2(false, false); }
 #undef FWD2
+      attn_note_fwd(AF_FWD2, drop, mask, false, false);
       return (int)hipGetLastError();
     }
     const int dm = drop ? (a.dbits ? 2 : 1) : 0;
@@ -2492,6 +2511,7 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
         if (dm == 2) { if (mask) DQ4(2, true); else DQ4(2, false); }
         else { if (mask) DQ4(0, true); else DQ4(0, false); }
 #undef DQ4
+        attn_note_bwd(AB_V4, dm, mask, 0, false);
         return (int)hipGetLastError();
       }
       dim3 grid((a.Lq + 127) / 128, a.B * a.H);
@@ -2500,6 +2520,7 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
       else if (dm == 1) { if (mask) DQ2(1, true); else DQ2(1, false); }
       else { if (mask) DQ2(0, true); else DQ2(0, false); }
 #undef DQ2
+      attn_note_bwd(AB_V2, dm, mask, 0, false);
       return (int)hipGetLastError();
     }
     if (which == 2) {
@@ -2509,12 +2530,14 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
         dim3 g4((a.Lk + 63) / 64, a.B * a.H);
         if (dm == 2) hipLaunchKernelGGL((dkv4_kernel<2>), g4, dim3(256), lds, s, a);
         else hipLaunchKernelGGL((dkv4_kernel<0>), g4, dim3(256), lds, s, a);
+        attn_note_dkv(AB_V4, dm, false, false);
         return (int)hipGetLastError();
       }
       dim3 grid((a.Lk + 127) / 128, a.B * a.H);
       if (dm == 2) hipLaunchKernelGGL((dkv2_kernel<2>), grid, dim3(256), 0, s, a);
       else if (dm == 1) hipLaunchKernelGGL((dkv2_kernel<1>), grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL((dkv2_kernel<0>), grid, dim3(256), 0, s, a);
+      attn_note_dkv(AB_V2, dm, false, false);
       return (int)hipGetLastError();
     }
     if (which == 4) {  // the 32x32x16 family: the fused launch for Lq <= 256 and Lk <= 512 (one or two key passes),
@@ -2531,6 +2554,7 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
       if (drop) { if (mask) BW3(2, true); else BW3(2, false); }
       else { if (mask) BW3(0, true); else BW3(0, false); }
 #undef BW3
+      attn_note_bwd(AB_BWD3S, drop ? 2 : 0, mask, 0, false);
       return (int)hipGetLastError();
     }
     return (int)hipErrorInvalidValue;
@@ -2538,12 +2562,15 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
     if (which == 0) {
       dim3 grid((a.Lq + 63) / 64, a.B * a.H);
       hipLaunchKernelGGL(fwd_kernel<T>, grid, dim3(256), 128 * RB, s, a);
+      attn_note_fwd(AF_GENERIC, drop, a.key_keep != nullptr, false, false);
     } else if (which == 1) {
       dim3 grid((a.Lq + 63) / 64, a.B * a.H);
       hipLaunchKernelGGL(dq_kernel<T>, grid, dim3(256), 192 * RB, s, a);
+      attn_note_bwd(AB_GENERIC, drop, a.key_keep != nullptr, 0, false);
     } else if (which == 2) {
       dim3 grid((a.Lk + 63) / 64, a.B * a.H);
       hipLaunchKernelGGL(dkv_kernel<T>, grid, dim3(256), 256 * RB + 512, s, a);
+      attn_note_dkv(AB_GENERIC, drop, false, false);
     } else {
       return (int)hipErrorInvalidValue;
     }
@@ -2589,6 +2616,8 @@ FDDM_API int fddm_attn_stamps_clear() {
 }
 #endif
 
+FDDM_API int fddm_attn_last_path(void) { return (int)((unsigned)g_last_fwd | ((unsigned)g_last_bwd << 16)); }
+
 FDDM_API int fddm_attn_set_kernels(int v6) {
   const int old = g_attn_v6;
   g_attn_v6 = (v6 >= 1 && v6 <= 5) ? v6 : 0;
@@ -2602,6 +2631,7 @@ static int attn_fwd_impl(int dtype, const void* Q, long sq, const void* K, long 
                          unsigned long long seed, unsigned long long stream, unsigned long long* drop_bits,
                          int drop_bits_ready, void* hs) {
   if (table && !gate) return (int)hipErrorInvalidValue;  // a bias table without its gate: no kernel takes that
+  attn_note_fwd(AF_NONE, 0, 0, false, false);
   AttnArgs a{};
   a.key_len = key_len;
   a.dbits = (uint64_t*)drop_bits;
@@ -2719,6 +2749,7 @@ static int attn_bwd_impl(int dtype, const void* Q, long sq, const void* K, long 
                          const int* key_len, int B, int H, int Lq, int Lk, float scale, float drop_p,
                          unsigned long long seed, unsigned long long stream, const unsigned long long* drop_bits,
                          void* hs) {
+  attn_note_bwd(AB_NONE, 0, 0, 0, false);
   AttnArgs a{};
   a.key_len = key_len;
   a.dbits = (uint64_t*)drop_bits;

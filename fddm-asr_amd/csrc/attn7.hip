@@ -1292,6 +1292,7 @@ int attn7_fwd(AttnArgs& a, hipStream_t s) {
   else { if (mk == 2) FWD7(0, 2); else if (mk == 1) FWD7(0, 1); else FWD7(0, 0); }
 #undef FWD7R
 #undef FWD7
+  attn_note_fwd(AF_FWD7, dm, mk, a.key_len && mk == 2, rel);
   return (int)hipGetLastError();
 }
 
@@ -1309,6 +1310,7 @@ int attn7_dq(AttnArgs& a, hipStream_t s) {
   else if (dm) { if (mk == 2) DQ7(1, 2); else if (mk == 1) DQ7(1, 1); else DQ7(1, 0); }
   else { if (mk == 2) DQ7(0, 2); else if (mk == 1) DQ7(0, 1); else DQ7(0, 0); }
 #undef DQ7
+  attn_note_bwd(AB_V7, dm, mk, 0, a.key_len && mk == 2);
   return (int)hipGetLastError();
 }
 
@@ -1324,6 +1326,7 @@ int attn7_dkv(AttnArgs& a, hipStream_t s) {
   else if (dm) { if (a.key_keep) DKV7(1, true); else DKV7(1, false); }
   else { if (a.key_keep) DKV7(0, true); else DKV7(0, false); }
 #undef DKV7
+  attn_note_dkv(AB_V7, dm, a.key_keep != nullptr, a.key_len && a.key_keep);
   return (int)hipGetLastError();
 }
 
@@ -1347,6 +1350,7 @@ int attn7_bwdf(AttnArgs& a, hipStream_t s) {
   }
 #undef BWF7X
 #undef BWF7
+  attn_note_bwd(AB_BWDF7, dm, a.key_keep != nullptr, a.Lk <= 256 ? 1 : 2, a.key_len && a.key_keep);
   return (int)hipGetLastError();
 }
 

@@ -730,6 +730,7 @@ int attn8_fwd(AttnArgs& a, hipStream_t s) {
   if (dm) { if (mk == 2) FWD8(1, 2); else if (mk == 1) FWD8(1, 1); else FWD8(1, 0); }
   else { if (mk == 2) FWD8(0, 2); else if (mk == 1) FWD8(0, 1); else FWD8(0, 0); }
 #undef FWD8
+  attn_note_fwd(AF_FWD8, dm, mk, false, false);
   return (int)hipGetLastError();
 }
 

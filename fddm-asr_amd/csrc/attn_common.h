@@ -106,6 +106,17 @@ __device__ __forceinline__ void pin16(uint4& x) {
   x = __builtin_bit_cast(uint4, v);
 }
 
+// Host-side record of the kernels the most recent forward and the most recent backward call launched
+// (fddm_attn_last_path, csrc/attention.hip): written by the launch wrappers, read by tests. No device code, no effect
+// on any launch. Forward word: bits 0-3 the kernel, 4-5 DM, 6-7 MK, 8 KX, 9 REL. Backward word: bits 0-3 the fused or
+// the dQ kernel, 4-5 DM, 6-7 its MK (dq7) / MASK (bwdf7, dq2, dq4, bwd3s) build, 8 the MASK build of dkv7, 9-10 NP,
+// 11 KX, 12-15 the dK / dV kernel of a pair (AB_DISAGREE: its DM or KX is not the dQ kernel's).
+enum { AF_NONE = 0, AF_FWD7, AF_FWD8, AF_FWD6, AF_FWD2, AF_FWD5, AF_GENERIC };
+enum { AB_NONE = 0, AB_BWDF7, AB_V7, AB_V2, AB_BWD3S, AB_V4, AB_GENERIC, AB_DISAGREE = 15 };
+void attn_note_fwd(int kernel, int dm, int mk, bool kx, bool rel);
+void attn_note_bwd(int kernel, int dm, int mk, int np, bool kx);  // the fused launch, or the dQ kernel of a pair
+void attn_note_dkv(int kernel, int dm, bool mask, bool kx);       // the dK / dV kernel after the dQ kernel noted before
+
 // csrc/attn7.hip: the 32x32x16-MFMA decoder forward (bf16, head_dim 64, Lk <= 1024, no dropout or keep bits already
 // written by fddm_attn_drop_bits)
 int attn7_fwd(AttnArgs& a, hipStream_t s);

@@ -133,6 +133,28 @@ def attn_force_kernels(name: str) -> str:
     return {v: k for k, v in ATTN_KERNELS.items()}[old]
 
 
+ATTN_FWD_KERNELS = ("none", "fwd7", "fwd8", "fwd6", "fwd2", "fwd5", "generic")
+ATTN_DQ_KERNELS = {0: "none", 1: "bwdf7", 2: "dq7", 3: "dq2", 4: "bwd3s", 5: "dq4", 6: "dq"}
+ATTN_DKV_KERNELS = {0: "", 2: "+dkv7", 3: "+dkv2", 5: "+dkv4", 6: "+dkv", 15: "+disagree"}
+
+
+def attn_last_path():
+    """The kernels the most recent attention forward call and the most recent attention backward call launched
+    (fddm_attn_last_path), as a dict:
+      fwd  (kernel, DM, MK, KX, REL): kernel one of ATTN_FWD_KERNELS and its template build
+      bwd  (kernels, DM, MK, dkv MASK, NP, KX): kernels "bwdf7", "bwd3s" or a pair such as "dq7+dkv7", "dq2+dkv2",
+           "dq2+dkv4" (ATTN_DQ_KERNELS + ATTN_DKV_KERNELS; the two launches are chosen separately); MK is dq7's MK or
+           the MASK build of bwdf7 / dq2 (0 / 1); dkv MASK is dkv7's; NP bwdf7's key passes (0 for the pairs)
+    A host-side record for tests, which must know the kernel they measured: attn_force_kernels only enables a family,
+    and a shape outside its preconditions takes another kernel."""
+    from ._lib import lib
+    v = lib().fddm_attn_last_path()
+    f, b = v & 0xFFFF, (v >> 16) & 0xFFFF
+    return {"fwd": (ATTN_FWD_KERNELS[f & 15], (f >> 4) & 3, (f >> 6) & 3, bool((f >> 8) & 1), bool((f >> 9) & 1)),
+            "bwd": (ATTN_DQ_KERNELS[b & 15] + ATTN_DKV_KERNELS[(b >> 12) & 15], (b >> 4) & 3, (b >> 6) & 3, (b >> 8) & 1,
+                    (b >> 9) & 3, bool((b >> 11) & 1))}
+
+
 def gemm(A, B, C, M, N, K, *, a_kc=True, b_kc=True, lda, ldb, ldc, epi=EPI_STORE, bias=None, alpha=1.0,
          C2=None, Mi=0, sAb=0, drop_p=0.0, seed=0, rng_stream=0, colsum=None):
     """C[m][n] = alpha * sum_k A(m,k) B(n,k) (+bias, epilogue). Compute dtype = B.dtype.
@@ -418,9 +440,11 @@ def attn_fwd_relgate(q, k, v, out, graw, gconst, table, B, H, L, scale=None):
 
 
 def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, *, key_keep=None, drop_p=0.0, seed=0, rng_stream=0,
-             dbits=None, scale=None, key_len=None):
+             dbits=None, scale=None, key_len=None, ws=None):
     """Gradients of attn_fwd (same layouts; head_dim = o.shape[1] // H, padded to 64 as in attn_fwd). key_len as in
-    attn_fwd (fddm_attn_bwd_kx: dk / dv rows at or past an entry's extent are exact zeros)."""
+    attn_fwd (fddm_attn_bwd_kx: dk / dv rows at or past an entry's extent are exact zeros). ws (optional): the
+    workspace to use instead of a fresh one, f32 with at least fddm_attn_bwd_ws_floats elements (the kernels write
+    every float they read back, so its contents do not matter; tests pass a NaN-filled one)."""
     _chk(o.shape[1] % H == 0, "attention output width must be H * head_dim")
     dh = o.shape[1] // H
     _chk(1 <= dh <= 64, f"head_dim {dh} > 64 is not built")
@@ -440,7 +464,11 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, *, key_keep=None, dr
         return
     # row-term workspace: delta = rowsum(dO O) and -LSE log2(e) per query, [2][B*H][Lq rounded up to 64] (the
     # 32x32x16 backward's layout; the other kernels use the first B*H*Lq floats)
-    delta = torch.empty(int(lib().fddm_attn_bwd_ws_floats(B, H, Lq, Lk)), device=q.device, dtype=torch.float32)
+    nws = int(lib().fddm_attn_bwd_ws_floats(B, H, Lq, Lk))
+    if ws is not None:
+        _chk(ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= nws and ws.device == q.device,
+             "attention backward workspace: contiguous f32, fddm_attn_bwd_ws_floats elements")
+    delta = ws if ws is not None else torch.empty(nws, device=q.device, dtype=torch.float32)
     if key_len is not None:
         call("fddm_attn_bwd_kx", code(q), ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(o),
              o.stride(0), ptr(do), do.stride(0), ptr(lse), ptr(dq), dq.stride(0), ptr(dk), dk.stride(0), ptr(dv),

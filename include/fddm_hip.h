@@ -293,6 +293,20 @@ int fddm_gemm_last_path(void);
  *      fwd7 with the bias). Returns the previous setting.
  *      Process-wide; the train step never sets it. */
 int fddm_attn_set_kernels(int v6);
+/* ---- which kernels the most recent attention forward call and the most recent attention backward call launched (a
+ *      host-side record for tests; no device code, no effect on any launch; each call clears its half first, so a call
+ *      that launched nothing reads 0 there). Bits 0-15, the forward: bits 0-3 the kernel — 0 none, 1 fwd7, 2 fwd8,
+ *      3 fwd6, 4 fwd2, 5 fwd5, 6 the generic kernel — bits 4-5 its DM build (dropout: 0 none, 1 recorded keep bits,
+ *      2 hashed in the kernel; fwd2 / generic: 0 / 1), bits 6-7 its MK build (0 no mask, 1 ragged Lk, 2 mask bytes;
+ *      fwd2 / fwd5 / generic: 0 / 1), bit 8 the length-bounded (KX) build, bit 9 the relative-position-bias build.
+ *      Bits 16-31, the backward: bits 16-19 the fused launch or the dQ kernel — 0 none, 1 bwdf7, 2 dq7, 3 dq2,
+ *      4 bwd3s, 5 dq4, 6 the generic dQ kernel — bits 20-21 DM (0 no dropout, 1 the 32x32x16 family's recorded bits or
+ *      dq2 / dkv2's rehash, 2 the round-4 recorded words), bits 22-23 the MK build of dq7 (0 / 1 / 2) or the MASK build
+ *      of bwdf7 / dq2 / dq4 / bwd3s (0 / 1), bit 24 the MASK build of dkv7, bits 25-26 bwdf7's key passes NP, bit 27 the
+ *      length-bounded (KX) builds, bits 28-31 the dK / dV kernel of a pair — 0 none, 2 dkv7, 3 dkv2, 5 dkv4, 6 generic,
+ *      15 one whose DM or KX is not the dQ kernel's (the two are chosen separately: beyond Lk 1024, dq2 runs with dkv4
+ *      up to Lq 1024 and with dkv2 beyond). Meaningful when the call returned 0. Process-wide, not thread-safe. */
+int fddm_attn_last_path(void);
 
 
 /* ---- dropout-seed offset for HIP-graph replays of the train step: every launch enqueued while `off` (a device u64)

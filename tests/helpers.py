@@ -1,4 +1,5 @@
 """Shared test helpers: PCG parameter dicts with reference names, fixture loading, comparisons."""
+import functools
 import os
 
 import numpy as np
@@ -822,3 +823,375 @@ def conv_ref(name, x, w, bias, dtype=torch.float64):
     s = F.conv1d(xt.abs(), w.to(dtype).abs(), bias.to(dtype).abs(), stride=g["stride"], padding=g["cpad"], groups=g["G"])
     assert y.shape[-1] == g["Tout"], (y.shape, g["Tout"])
     return (y.transpose(1, 2).reshape(g["Bn"] * g["Tout"], -1), s.transpose(1, 2).reshape(g["Bn"] * g["Tout"], -1))
+
+
+# ------------------------------------------------------------------ attention backward (csrc/attn7.hip, csrc/attention.hip)
+# Reference, per-element units, rounding-point emulation, inputs and the case table shared by
+# tests/test_cpu_attn_bwd_ref.py (which sets the constants below from the reference alone and proves with mutated
+# references that the bound tells real bugs apart) and tests/test_gpu_attn_bwd.py (which runs the kernels).
+U9 = 2.0 ** -9                 # half an ulp of bf16, relative
+LOG2E_F32 = float(np.float32(1.4426950408889634))
+LN2_F32 = float(np.float32(0.6931471805599453))
+ATTN_SEED, ATTN_STREAM = 5, 9  # the dropout site of every attention-backward case
+
+
+def attn_p32(p):
+    """The dropout probability as the C ABI receives it."""
+    return float(np.float32(p))
+
+
+class AttnBwdTerms:
+    """Float64 pieces of one attention backward: S, P, G, delta, T, PD (= P o D), D (float), c, and dq / dk / dv."""
+    __slots__ = ("S", "P", "G", "delta", "T", "PD", "D", "c", "dq", "dk", "dv")
+
+
+def attn_fwd_ref64(q, k, v, keep, drop_keep, p, scale):
+    """Float64 forward: q [B, H, Lq, 64], k, v [B, H, Lk, 64] (any float dtype), keep [B, Lk] bool or None, drop_keep
+    [B, H, Lq, Lk] bool or None (oracle.attn_dropout_keep). Returns O [B, H, Lq, 64] and LSE [B, H, Lq] (natural log of
+    the scaled scores), both float64."""
+    s = float(scale) * (q.double() @ k.double().transpose(-1, -2))
+    if keep is not None:
+        s = s.masked_fill(~keep[:, None, None, :], float("-inf"))
+    lse = torch.logsumexp(s, -1)
+    pr = torch.exp(s - lse[..., None])
+    if drop_keep is not None:
+        pr = pr * drop_keep.double() / (1.0 - float(p))
+    return pr @ v.double(), lse
+
+
+def attn_bwd_terms64(q, k, v, do, o, lse, keep, drop_keep, p, scale, *, c_on_g=True):
+    """S, P, G, delta, T, PD of attn_bwd_ref64 (below), without the three products. c_on_g=False leaves the dropout
+    scale off G (a mutant of tests/test_cpu_attn_bwd_ref.py)."""
+    t = AttnBwdTerms()
+    q, k, v, do, o, lse = (x.double() for x in (q, k, v, do, o, lse))
+    t.c = 1.0 / (1.0 - float(p)) if drop_keep is not None else 1.0
+    t.S = float(scale) * (q @ k.transpose(-1, -2))
+    t.P = torch.exp(t.S - lse[..., None])
+    if keep is not None:
+        t.P = t.P * keep[:, None, None, :].double()
+    t.D = drop_keep.double() if drop_keep is not None else torch.ones_like(t.P)
+    t.G = do @ v.transpose(-1, -2)
+    t.delta = (do * o).sum(-1)
+    t.T = t.P * ((t.c if c_on_g else 1.0) * t.D * t.G - t.delta[..., None])
+    t.PD = t.P * t.D
+    return t
+
+
+def attn_bwd_products64(t, q, k, do, scale):
+    """dQ = s T K, dK = s T^T Q, dV = c (P o D)^T dO into t.dq / t.dk / t.dv; returns t."""
+    t.dq = float(scale) * (t.T @ k.double())
+    t.dk = float(scale) * (t.T.transpose(-1, -2) @ q.double())
+    t.dv = t.c * (t.PD.transpose(-1, -2) @ do.double())
+    return t
+
+
+def attn_bwd_ref64(q, k, v, do, o, lse, keep, drop_keep, p, scale):
+    """The operation fddm_attn_bwd defines, in float64 on the values the kernel receives: bf16 Q, K, V, dO, O as
+    [B, H, L, 64] and the fp32 LSE [B, H, Lq] (O and LSE are inputs of the backward, not recomputed: the reference is
+    exact for whatever forward produced them). keep [B, Lk] bool or None is the key mask M (keys past an extent are
+    masked keys), drop_keep [B, H, Lq, Lk] bool or None the keep bits D of oracle.attn_dropout_keep, c = 1 / (1 - p)
+    with p as given (attn_p32(p) is what the C ABI receives, a float32), s = scale:
+        S = s Q K^T      P = exp(S - LSE), 0 where M is false      G = dO V^T
+        delta_i = sum_d dO_id O_id      T = P o (c D o G - delta)
+        dQ = s T K       dK = s T^T Q       dV = c (P o D)^T dO
+    Returns an AttnBwdTerms. dK / dV rows of masked keys are exact zeros (their P column is)."""
+    return attn_bwd_products64(attn_bwd_terms64(q, k, v, do, o, lse, keep, drop_keep, p, scale), q, k, do, scale)
+
+
+def attn_bwd_units(t, q, k, v, do, o, scale):
+    """Root-sum-square error units (b_dQ, b_dK, b_dV) of an AttnBwdTerms, for the check
+        |gpu - ref| <= C u b + 2^-8 |ref|,   u = 2^-9.
+    The bf16 rounding points of the kernels, each a relative error of at most u on the value it rounds:
+      (1) Q' = bf16(Q s log2 e), the score operand (attn7.hip scale_frag: dq7 :588, bwdf7 :1035; dkv7 streams the Q'
+          dq7 wrote, :725-729 / :790). It moves S_ik by sum_d dQ'_id K_kd, of root-sum-square size u a_ik with
+          a_ik = s sqrt(sum_d Q_id^2 K_kd^2), and with it P_ik, T_ik and (P D)_ik by the factor a_ik u.
+      (2) T packed to bf16 before the second MFMAs (dq7 :695, dkv7 :903-904, bwdf7 :1161-1165).
+      (3) P o D packed to bf16 before the dV MFMA (dkv7 :901-902, bwdf7 :1159-1160); dq7 never rounds P itself.
+      (4) dK formed from Q' (the ring's image, dkv7 :916-919, bwdf7 :1177-1180) and multiplied by ln 2 = s / (s log2 e)
+          (:939, :1241): the rounding (1) enters dK a second time, as T_ik dQ'_id.
+      (5) -LSE log2 e as a bf16 pair hi + lo (neg_split, dq7 :602; dkv7 :866-869; bwdf7 :1125-1128): 2^-18 |LSE| on the
+          exponent, fp32-sized, not counted.
+      (6) dQ, dK, dV rounded to bf16 (dq7 :739, dkv7 :949, bwdf7 :1218 / :1252): the 2^-8 |ref| term.
+      (7) G_ik = sum_d dO_id V_kd (the dP MFMAs, dq7 :676, dkv7 :875, bwdf7 :1134) and delta_i = sum_d dO_id O_id (dq7
+          :592-595, bwdf7 :1029-1033) are fp32 sums of 64 products each, subtracted from one another (:687-693, :894-897,
+          :1152-1155). The fp32 rounding of a sum of n products is taken as sqrt(n) 2^-24 of the root-sum-square of
+          the products (each of the n partial sums rounds once, and a partial sum grows like the root-sum-square), here
+          2^-21 h_ik = 2^-12 u h_ik with h_ik^2 = sum_d dO_id^2 ((c D_ik V_kd)^2 + O_id^2). Next to (1) and (2) it is
+          2^-12 of nothing in general; it is the whole error where c D G - delta cancels: an entry with one kept key
+          and no dropout has O = V, T = 0 and dQ = dK = 0 in the reference, and the kernels' T is the difference of two
+          fp32 sums taken in different orders.
+    Everything else is fp32 and not counted: the score MFMA accumulators, exp2, the final scalings, the f32 dQ partial
+    bwdf7 keeps in the workspace between its two key passes. dq2 / dkv2 (attention.hip :1363-1723) round at (2), (3),
+    (6) and (7) only: the score operand is Q itself, S s log2 e - LSE log2 e is fp32 (:1490, :1668), dK = s T^T Q
+    (:1711). With e_ik^2 = T_ik^2 (1 + a_ik^2) + (2^-12 P_ik h_ik)^2:
+        b_dQ[i, d] = s sqrt(sum_k e_ik^2 K_kd^2)
+        b_dK[k, d] = s sqrt(sum_i (e_ik^2 + T_ik^2) Q_id^2)
+        b_dV[k, d] = c sqrt(sum_i (P D)_ik^2 (1 + a_ik^2) dO_id^2)"""
+    q2, k2, v2, do2, o2 = (x.double() ** 2 for x in (q, k, v, do, o))
+    s = float(scale)
+    a2 = s * s * (q2 @ k2.transpose(-1, -2))
+    T2 = t.T ** 2
+    h2 = (t.c * t.D) ** 2 * (do2 @ v2.transpose(-1, -2)) + (do2 * o2).sum(-1)[..., None]
+    e2 = T2 * (1.0 + a2) + 2.0 ** -24 * t.P ** 2 * h2
+    b_dq = s * torch.sqrt(e2 @ k2)
+    b_dk = s * torch.sqrt((e2 + T2).transpose(-1, -2) @ q2)
+    b_dv = t.c * torch.sqrt((t.PD ** 2 * (1.0 + a2)).transpose(-1, -2) @ do2)
+    return b_dq, b_dk, b_dv
+
+
+def _bf(x):
+    return x.to(torch.bfloat16).float()
+
+
+def attn_bwd_emulate(q, k, v, do, o, lse, keep, drop_keep, p, scale, family="7"):
+    """The kernels' rounding points in plain torch: fp32 where the kernel holds fp32, .to(bfloat16) at the points (1)-(6)
+    of attn_bwd_units. family "7": bwdf7 / dq7 / dkv7; family "2": dq2 / dkv2 (no Q' rounding, fp32 LSE, dK from Q with
+    the scale). Not modelled: the MFMA summation order, the hardware exp2, FMA contraction other than c D G - delta.
+    It sets the constants ATTN_BWD_E and proves statements about inputs; it is no oracle for the kernels. Returns
+    (dq, dk, dv) float32 holding bf16 values."""
+    f32 = torch.float32
+    q, k, v, do, o = (x.to(f32) for x in (q, k, v, do, o))
+    sc = float(np.float32(scale))
+    sl2 = float(np.float32(sc * LOG2E_F32))
+    lse2 = lse.to(f32) * LOG2E_F32
+    if family == "7":
+        qp = _bf(q * sl2)
+        hi = _bf(-lse2)
+        lo = _bf(-lse2 - hi)
+        arg = (hi + lo)[..., None] + qp @ k.transpose(-1, -2)
+    else:
+        qp = q
+        arg = (q @ k.transpose(-1, -2)) * sl2 - lse2[..., None]
+    P = torch.exp2(arg)
+    if keep is not None:
+        P = P * keep[:, None, None, :].to(f32)
+    G = do @ v.transpose(-1, -2)
+    delta = (do * o).sum(-1)
+    if drop_keep is not None:
+        c = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+        D = drop_keep.to(f32)
+        X = (G.double() * D.double() * c - delta.double()[..., None]).to(f32)      # one fmaf
+    else:
+        c, D = 1.0, torch.ones_like(P)
+        X = G - delta[..., None]
+    T = _bf(P * X)
+    PD = _bf(P * D)
+    dq = _bf((T @ k) * sc)
+    dk = _bf((T.transpose(-1, -2) @ qp) * (LN2_F32 if family == "7" else sc))
+    dv = _bf((PD.transpose(-1, -2) @ do) * c)
+    if keep is not None:       # masked keys: the kernels store zeros whatever the accumulators hold
+        z = keep[:, None, :, None].to(f32)
+        dk, dv = dk * z, dv * z
+    return dq, dk, dv
+
+
+def attn_bwd_excess(got, ref, b):
+    """(|got - ref| - 2^-8 |ref|)+ in units of u b, per element; 0 where b == 0 and got == ref, inf where b == 0 and
+    they differ. The check |got - ref| <= C u b + 2^-8 |ref| is attn_bwd_excess <= C."""
+    x = ((got.double() - ref).abs() - 2.0 ** -8 * ref.abs()).clamp_min(0.0)
+    out = x / (U9 * b)
+    out = torch.where(b == 0, torch.where(x == 0, torch.zeros_like(x), torch.full_like(x, float("inf"))), out)
+    return out
+
+
+# The largest error of attn_bwd_emulate against attn_bwd_ref64 in units of u b (after the 2^-8 |ref| term), over every
+# case of attn_bwd_cases() and every input set, per kernel family and output, measured on the CPU
+# (tests/test_cpu_attn_bwd_ref.py asserts the measured values stay at or below these). The kernels are allowed
+# ATTN_BWD_C = 2 E units: what the emulation leaves out is fp32-sized (about 2^-15 of the counted terms), and a flipped
+# bf16 tie of T is a counted term, so the factor covers only the tail between one sample of roundings and another.
+# Measured: family 7 (bwdf7, dq7 / dkv7) dq 3.85, dk 4.00, dv 3.95; family 2 (dq2 with dkv2 or dkv4) dq 2.27, dk 2.36,
+# dv 2.60; the constants keep about 10 % headroom.
+ATTN_BWD_E = {"7": dict(dq=4.2, dk=4.4, dv=4.3), "2": dict(dq=2.5, dk=2.6, dv=2.8)}
+ATTN_BWD_C = {f: {n: 2.0 * e for n, e in d.items()} for f, d in ATTN_BWD_E.items()}
+
+ATTN_EDGE_KEYS = (0, 31, 32, 63, 64, 127, 128, 255, 256)
+ATTN_EDGE_QUERIES = (0, 31, 32, 63, 64, 127, 128)
+ATTN_EDGE_DO = 32.0            # dO rows of edge queries, a power of two
+ATTN_EDGE_QSTD = 0.5           # the random part of every query
+ATTN_EDGE_QW = 4.0             # every query's component along w
+ATTN_EDGE_MASS = 1.0           # edge keys : other keys, the ratio of probability mass the edge keys are sized for
+
+
+def attn_bwd_mask(B, Lk, ext=None):
+    """The key masks of the cases (tests/test_gpu_lengths.py's): keep [B, Lk] bool.
+    ext given (length-bounded cases): keys below each entry's extent, with a hole of three keys (10..12) and a whole
+    masked 64-key tile (64..127) in entry 0 and the key before the last masked in the last entry.
+    ext None: entry 0 gets the same holes, the last entry a padded tail of 9 keys and the key before its last masked.
+    Every hole stays inside the kept range; an entry never loses its last key (or its only one)."""
+    e = torch.tensor(ext if ext is not None else [Lk] * (B - 1) + [max(1, Lk - 9)])
+    keep = torch.arange(Lk)[None, :] < e[:, None]
+    e0, el = int(e[0]), int(e[B - 1])
+    if e0 > 13:
+        keep[0, 10:13] = False
+    if e0 > 128:
+        keep[0, 64:128] = False
+    if el >= 3:
+        keep[B - 1, el - 2] = False
+    return keep
+
+
+def _attn_edge_keys(keep_b, Lk):
+    """Edge keys of one entry: ATTN_EDGE_KEYS, Lk - 1, extent - 1 and the key after each hole, where kept."""
+    kept = keep_b.nonzero().flatten().tolist()
+    last = kept[-1]
+    edges = set(ATTN_EDGE_KEYS) | {Lk - 1, last}
+    edges |= {j for j in kept if j > 0 and not keep_b[j - 1]}
+    return sorted(j for j in edges if j <= last and keep_b[j])
+
+
+def _c(fam, Lq, Lk, masked, p, *, ext=None, force="auto", rehash=False, strided=False, guard=False, peaked=False,
+       B=2, H=2, chain=False):
+    """One case. fam: "bwdf7" | "pair7" | "pair2"; expect: what ops.attn_last_path()["bwd"] must read."""
+    kx = ext is not None
+    if kx:
+        B, masked = len(ext), True
+    dm = 0 if p == 0 else 1
+    if fam == "bwdf7":
+        expect = ("bwdf7", dm, int(masked), 0, 1 if Lk <= 256 else 2, kx)
+    elif fam == "pair7":
+        mk = 2 if masked else 1 if Lk % 64 else 0
+        expect = ("dq7+dkv7", dm, mk, int(masked), 0, kx)
+    else:
+        # the dK / dV launch is chosen on its own (attention.hip run<>, which == 2): dkv2 when it rehashes or Lq > 1024,
+        # else the round-4 dkv4, which is therefore what the default dispatch runs beside dq2 at Lk > 1024
+        dm = 0 if p == 0 else 1 if rehash else 2
+        expect = ("dq2+dkv2" if rehash or Lq > 1024 else "dq2+dkv4", dm, int(masked or Lk % 64 != 0), 0, 0, False)
+    cid = (f"{fam}-{Lq}x{Lk}" + ("-" + "_".join(map(str, ext)) if kx else "") + ("-mask" if masked and not kx else "")
+           + (f"-p{p}" if p else "") + ("-rehash" if rehash else "") + (f"-{force}" if force != "auto" else "")
+           + ("-strided" if strided else "") + ("-guard" if guard else "") + ("-peaked" if peaked else ""))
+    return dict(id=cid, fam=fam, family="2" if fam == "pair2" else "7", B=B, H=H, Lq=Lq, Lk=Lk, masked=masked, p=p,
+                ext=ext, force=force, rehash=rehash, strided=strided, guard=guard, peaked=peaked, expect=expect,
+                chain=chain or kx)
+
+
+ATTN_KX = {200: [200, 1, 63, 64, 65, 129], 300: [300, 257, 256, 70]}   # one, then two, live key passes of bwdf7
+
+
+def attn_bwd_cases():
+    """Every case of tests/test_gpu_attn_bwd.py: the smallest shapes at which each mechanism of each backward kernel
+    exists (B H <= 8). guard: dq / dk / dv are column slices of wider NaN-filled buffers; strided: q, k, v are column
+    slices of one [rows, 3 H 64] buffer; chain: the case also runs behind ops.attn_fwd (fwd7 and forced fwd8)."""
+    cs = []
+    n = 0
+    for fam, force, shapes in (
+            # one key pass: one query and key | a partial 32-query group, five keys | two query tiles, 17 keys | exactly
+            # one tile | three query tiles, ragged fourth key tile | four full tiles of each
+            ("bwdf7", "auto", ((1, 1), (33, 5), (65, 17), (64, 64), (129, 200), (256, 256))),
+            # two key passes: one key in the second | a ragged second pass | both full
+            ("bwdf7", "auto", ((40, 257), (129, 300), (256, 512))),
+            # the split pair by default: Lq > 256 (MK 0 and MK 1) | 512 < Lk <= 1024 (MK 1 and MK 0)
+            ("pair7", "auto", ((257, 64), (300, 200), (40, 513), (96, 1024))),
+            # ... and forced at the fused launch's shapes
+            ("pair7", "nofused", ((65, 17), (129, 200), (129, 300)))):
+        for Lq, Lk in shapes:
+            for masked in (False, True):
+                for p in (0.0, 0.1):
+                    cs.append(_c(fam, Lq, Lk, masked, p, force=force, guard=p > 0 and masked,
+                                 chain=n % 4 == (n // 4) % 4))     # one of a shape's four variants, in rotation
+                    n += 1
+    for fam, force in (("bwdf7", "auto"), ("pair7", "nofused")):
+        for Lk, ext in ATTN_KX.items():
+            for p in (0.0, 0.1):
+                cs.append(_c(fam, 129, Lk, True, p, ext=ext, force=force, H=1 if Lk == 200 else 2, guard=p > 0))
+        # q, k, v from one fused-projection buffer; a peaked softmax (flat inputs with q x 3)
+        cs.append(_c(fam, 129, 200, True, 0.1, force=force, strided=True, chain=True))
+        cs.append(_c(fam, 129, 200, True, 0.1, force=force, peaked=True))
+    # dq2 (+ dkv4 up to Lq 1024, dkv2 beyond): Lk > 1024 with recorded bits (DM 2) and without dropout (DM 0): one key in
+    # the 17th tile | two query blocks, 18 tiles | Lk a multiple of 64 (the unmasked builds); dq2 + dkv2 at any Lk when
+    # the kernels rehash (DM 1)
+    for Lq, Lk in ((40, 1025), (130, 1100)):
+        for masked in (False, True):
+            for p in (0.0, 0.1):
+                cs.append(_c("pair2", Lq, Lk, masked, p, guard=p > 0 and masked))
+    for p in (0.0, 0.1):
+        cs.append(_c("pair2", 40, 1088, False, p, B=1))
+        # Lq > 1024 as well: dkv2 without dropout and with recorded bits (17 query tiles, one query in the last)
+        cs.append(_c("pair2", 1025, 1088, False, p, B=1, H=1))
+        cs.append(_c("pair2", 1025, 1030, p > 0, p, B=1, H=1, guard=p > 0))
+    for Lq, Lk in ((130, 70), (64, 128)):
+        for masked in (False, True):
+            cs.append(_c("pair2", Lq, Lk, masked, 0.1, rehash=True, guard=masked))
+    assert len({c["id"] for c in cs}) == len(cs)
+    return cs
+
+
+# the template builds the case table must reach (attention.hip run<>, attn7.hip attn7_bwdf / attn7_dq / attn7_dkv), as
+# ops.attn_last_path()["bwd"] reads them: every (MASK / MK, NP, KX) combination with and without dropout
+ATTN_BWD_BUILDS = (
+    [("bwdf7", dm, mask, 0, np_, False) for dm in (0, 1) for mask in (0, 1) for np_ in (1, 2)] +
+    [("bwdf7", dm, 1, 0, np_, True) for dm in (0, 1) for np_ in (1, 2)] +
+    # dq7 <DM, MK, KX> with dkv7 <DM, MASK, KX>: MASK = a mask was passed, which is MK == 2
+    [("dq7+dkv7", dm, mk, int(mk == 2), 0, False) for dm in (0, 1) for mk in (0, 1, 2)] +
+    [("dq7+dkv7", dm, 2, 1, 0, True) for dm in (0, 1)] +
+    [("dq2+dkv2", dm, mask, 0, 0, False) for dm in (0, 1, 2) for mask in (0, 1)] +
+    # dq2 <DM, MASK> beside dkv4 <DM>: Lk > 1024 with Lq <= 1024
+    [("dq2+dkv4", dm, mask, 0, 0, False) for dm in (0, 2) for mask in (0, 1)])
+
+
+@functools.lru_cache(maxsize=None)
+def attn_bwd_case_inputs(cid, kind):
+    """Inputs of case `cid` for input set `kind`, built once and never modified: a dict of
+      q, do [B, Lq, H 64], k, v [B, Lk, H 64] float32 holding bf16 values; keep [B, Lk] bool or None; drop [B, H, Lq, Lk]
+      bool or None (the oracle's keep bits at ATTN_SEED / ATTN_STREAM); edge_keys (per entry), edge_queries.
+    "flat": randn q, k, v, dO (q x 3 in a peaked case).
+    "edges": q = 0.5 randn + 4 w for one unit vector w (64 entries of +-1/8), every edge key of an entry (ATTN_EDGE_KEYS,
+      Lk - 1, each extent - 1, the key after each hole) gets + beta w with beta = 2 ln(kept keys / edge keys), so that
+      the edge keys together hold about half of each row's probability mass (the extra scaled score of an edge key is
+      beta / 2); masked keys get the same + beta w (no effect on the reference; a kernel that keeps one shows it);
+      dO rows of the edge queries (ATTN_EDGE_QUERIES, Lq - 1) are multiplied by ATTN_EDGE_DO = 32. The halved random
+      part of q keeps the edge keys' probabilities within a factor of about two of one another (at full size the
+      scores' randn part spreads them over e^+-1.1 and a single edge key often carries too little of its row), the
+      factor 32 lets the at most 8 edge queries outweigh up to 248 others in dK and dV: with 4 w on a full-size q and a
+      factor 8 the mutants of tests/test_cpu_attn_bwd_ref.py left the bound on 0.47-0.56 of their elements at
+      Lk >= 300, with these on 0.64 or more."""
+    import math
+    from oracle import fddm_oracle as O
+    c = {x["id"]: x for x in attn_bwd_cases()}[cid]
+    B, H, Lq, Lk, p = c["B"], c["H"], c["Lq"], c["Lk"], c["p"]
+    gen = torch.Generator().manual_seed(7919 * Lq + 31 * Lk + (1 if kind == "edges" else 0))
+    q, k, v, do = (torch.randn(B, L, H, 64, generator=gen) for L in (Lq, Lk, Lk, Lq))
+    keep = attn_bwd_mask(B, Lk, c["ext"]) if c["masked"] else None
+    full = torch.ones(B, Lk, dtype=torch.bool) if keep is None else keep
+    ek = [_attn_edge_keys(full[b], Lk) for b in range(B)]
+    eq = sorted({j for j in ATTN_EDGE_QUERIES + (Lq - 1,) if j < Lq})
+    if kind == "edges":
+        w = (torch.randint(0, 2, (64,), generator=gen).float() * 2.0 - 1.0) / 8.0
+        q = ATTN_EDGE_QSTD * q + ATTN_EDGE_QW * w
+        for b in range(B):
+            nk = int(full[b].sum())
+            beta = max(0.0, 8.0 / ATTN_EDGE_QW * math.log(ATTN_EDGE_MASS * nk / len(ek[b])))
+            k[b, ek[b]] += beta * w
+            k[b, (~full[b]).nonzero().flatten()] += beta * w
+        do[:, eq] *= ATTN_EDGE_DO
+    elif c["peaked"]:
+        q = q * 3.0
+    rnd = lambda x, L: x.to(torch.bfloat16).float().reshape(B, L, H * 64)  # noqa: E731
+    drop = O.attn_dropout_keep(ATTN_SEED, ATTN_STREAM, B, H, Lq, Lk, p) if p > 0 else None
+    return dict(q=rnd(q, Lq), k=rnd(k, Lk), v=rnd(v, Lk), do=rnd(do, Lq), keep=keep, drop=drop, edge_keys=ek,
+                edge_queries=eq)
+
+
+def attn_heads(x, B, H):
+    """[B, L, H 64] or [B L, H 64] -> [B, H, L, 64]."""
+    return x.reshape(B, -1, H, 64).transpose(1, 2)
+
+
+def attn_rows(t):
+    """[B, H, L, 64] -> [B L, H 64]."""
+    B, H, L, _ = t.shape
+    return t.transpose(1, 2).reshape(B * L, H * 64)
+
+
+@functools.lru_cache(maxsize=None)
+def attn_bwd_case_ref(cid, kind):
+    """The isolated mode's O = bf16(float64 forward) and LSE = fp32(float64 LSE) of a case, with the float64 reference
+    of the backward that receives them and its units: (o [B, H, Lq, 64] float32 holding bf16 values, lse [B, H, Lq]
+    float32, out64 [B, H, Lq, 64], lse64, AttnBwdTerms, (b_dQ, b_dK, b_dV)). Built once, never modified."""
+    c = {x["id"]: x for x in attn_bwd_cases()}[cid]
+    x = attn_bwd_case_inputs(cid, kind)
+    B, H = c["B"], c["H"]
+    q, k, v, do = (attn_heads(x[n], B, H) for n in ("q", "k", "v", "do"))
+    o64, lse64 = attn_fwd_ref64(q, k, v, x["keep"], x["drop"], attn_p32(c["p"]), 0.125)
+    o, lse = o64.to(torch.bfloat16).float(), lse64.float()
+    t = attn_bwd_ref64(q, k, v, do, o, lse, x["keep"], x["drop"], attn_p32(c["p"]), 0.125)
+    return o, lse, o64, lse64, t, attn_bwd_units(t, q, k, v, do, o, 0.125)
