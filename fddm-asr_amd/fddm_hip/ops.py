@@ -296,7 +296,16 @@ def posconv_gelu(x, W, bias, out, B, S, E, G, kp):
 
 
 def conv0_gn_gelu(wave, w, gamma, beta, out_dtype, C, K, S, eps=1e-5):
+    """WavLM conv layer 0 + GroupNorm(C groups) + GELU: wave [B, nsamp] f32, w [C, K] f32 -> [B, T0, C] (f32 / bf16)."""
+    _chk(wave.dim() == 2 and wave.is_contiguous() and wave.dtype == torch.float32,
+         "conv0: wave is contiguous f32 [B, nsamp]")
+    _chk(K == 10 and C % 2 == 0, "conv0: kernel width 10, an even channel count")
+    _chk(w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (C, K), "conv0: w is contiguous f32 [C, K]")
+    _chk(gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == C and beta.numel() == C
+         and gamma.is_contiguous() and beta.is_contiguous(), "conv0: gamma and beta are f32 [C]")
+    _chk(out_dtype in (torch.float32, torch.bfloat16), "conv0: f32 or bf16 output")
     B, nsamp = wave.shape
+    _chk(nsamp >= K, "conv0: an utterance shorter than the kernel")
     T0 = (nsamp - K) // S + 1
     nb = (T0 + 4095) // 4096  # statistics blocks per utterance (wavlm.hip C0_GRAM_FRAMES)
     ws = torch.empty(B * nb * (K + K * (K + 1) // 2) + B * C, device=wave.device, dtype=torch.float64)
@@ -307,7 +316,18 @@ def conv0_gn_gelu(wave, w, gamma, beta, out_dtype, C, K, S, eps=1e-5):
 
 
 def wavlm_gate(x2d, W, bias, cst, B, S, H):
+    """Gated relative-position gate: x2d [B*S, E] (f32 / bf16), W [8, E/H] f32, bias [8], cst [H] -> [B*H, S] f32."""
+    _chk(x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype in (torch.float32, torch.bfloat16),
+         "wavlm_gate: x is contiguous f32 / bf16 [B*S, E]")
+    _chk(H > 0 and x2d.shape[0] == B * S, "wavlm_gate: x has B*S rows, H > 0")
     E = x2d.shape[1]
+    _chk(E % H == 0, "wavlm_gate: E is a multiple of H")
+    dh = E // H
+    _chk(dh % 8 == 0 and 0 < dh <= 64, "wavlm_gate: head width a multiple of 8, at most 64")
+    _chk(W.dtype == torch.float32 and W.is_contiguous() and tuple(W.shape) == (8, dh),
+         "wavlm_gate: W is contiguous f32 [8, dh]")
+    _chk(bias.dtype == torch.float32 and tuple(bias.shape) == (8,) and bias.is_contiguous(), "wavlm_gate: bias is f32 [8]")
+    _chk(cst.dtype == torch.float32 and tuple(cst.shape) == (H,) and cst.is_contiguous(), "wavlm_gate: cst is f32 [H]")
     gate = torch.empty(B * H, S, device=x2d.device, dtype=torch.float32)
     call("fddm_wavlm_gate", code(x2d), ptr(x2d), ptr(W), ptr(bias), ptr(cst), ptr(gate), B, S, H, E, stream())
     return gate

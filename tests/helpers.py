@@ -463,6 +463,16 @@ GEMM_DGELU_REL = 2e-6          # gelu_grad: |err| <= 2e-6 |y| (common.h document
 # epilogue's roundings. Hard cap 64.
 GEMM_E = {"f32": 3.8, "bf16": 3.1, "conv-f32": 7.3, "conv-bf16": 5.9}
 GEMM_C = {k: 8.0 * v for k, v in GEMM_E.items()}
+# The WavLM front end (csrc/wavlm.hip, csrc/posconv.hip; the section at the end of this file), in the same way:
+U18 = 2.0 ** -18               # conv0_mfma: v = hi + lo leaves <= 2^-18 |v|, the dropped lo * lo term is of that order
+# fp32 (resp. hi/lo bf16 split) evaluation in each kernel's order against float64, in units of 2^-24 s (conv0_split:
+# 2^-18 s), the maximum over every case of the tables below, measured on the CPU: 4.65, 4.26, 1.36, 2.18
+# (tests/test_cpu_wavlm_front_ref.py asserts them; the constants keep 10 % headroom). The kernels are allowed
+# FRONT_C = 8 E units: the margin covers the MFMA-internal summation order, packed-FMA contraction, the roundings of sc
+# and sh and the fast exp / rcp. Hard cap 64.
+FRONT_E = {"conv0_f32": 5.1, "conv0_split": 4.65, "posconv": 1.49, "gate": 2.39}
+FRONT_C = {k: 8.0 * v for k, v in FRONT_E.items()}
+FRONT_E_FLOOR = 0.05           # stored <= 1.1 measured + this
 
 
 class GemmRef:
@@ -1195,3 +1205,306 @@ def attn_bwd_case_ref(cid, kind):
     o, lse = o64.to(torch.bfloat16).float(), lse64.float()
     t = attn_bwd_ref64(q, k, v, do, o, lse, x["keep"], x["drop"], attn_p32(c["p"]), 0.125)
     return o, lse, o64, lse64, t, attn_bwd_units(t, q, k, v, do, o, 0.125)
+
+
+# ------------------------------------------------------------ WavLM front end (csrc/wavlm.hip, csrc/posconv.hip)
+# Reference, per-element bounds, inputs and case tables shared by tests/test_cpu_wavlm_front_ref.py (which sets the
+# constants below from the reference alone) and tests/test_gpu_wavlm_front.py (which runs the kernels).
+def bf16_round_bound(ref, b):
+    """b plus one rounding to nearest bf16 of a value within b of ref: b + 2^(floor(log2(|ref| + b)) - 8), the exact
+    half ulp (0 where |ref| + b is 0)."""
+    m = ref.abs() + b
+    _, e = torch.frexp(m)                      # m = f 2^e, f in [0.5, 1): floor(log2 m) = e - 1
+    half = torch.ldexp(torch.ones_like(m), e - 9)
+    return b + torch.where(m > 0, half, torch.zeros_like(m))
+
+
+def _bf32(x):
+    return x.to(torch.bfloat16).to(torch.float32)
+
+
+def _fma32(a, b, c):
+    """fp32 fma(a, b, c): the product of two floats is exact in float64."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+class Conv0Ref:
+    """y, ya = |x| * |w| [B, T0, C]; sc, sh [B, C]; z = sc y + sh with error scale s; ref = gelu(z); lin = |gelu'(z)|."""
+    __slots__ = ("y", "ya", "sc", "sh", "z", "s", "ref", "lin")
+
+
+class PosconvRef:
+    """y [B, S, E] with error scale s; ref = gelu(y); lin = |gelu'(y)|; full: the S + 1 frames of the padded conv."""
+    __slots__ = ("y", "s", "ref", "lin", "full")
+
+
+class GateRef:
+    """pa, pb [B, S, H] with error scales sa, sb; ref [B, H, S]; da, db = |d gate / d pa|, |d gate / d pb|; A: the
+    absolute allowance."""
+    __slots__ = ("pa", "pb", "sa", "sb", "ref", "da", "db", "A")
+
+
+# ---- conv layer 0 + GroupNorm + GELU
+CONV0_K, CONV0_S, CONV0_EPS, CONV0_TAIL = 10, 5, 1e-5, 3
+CONV0_KINDS = {"loud": (3.0, 0.0), "plain": (0.1, 0.0), "dc": (0.05, 0.4), "quiet": (1e-4, 0.0), "silent": (0.0, 0.0)}
+CONV0_MIX = ("loud", "plain", "dc")
+CONV0_EXPOSED = ("dc", "quiet", "silent")
+# (id, path, C, T0s, utterance kinds): path "mfma" (bf16 out, C % 512 == 0), "f32" (conv0_apply<float>), "bf16"
+# (conv0_apply<bf16_t>)
+CONV0_CASES = [
+    ("mfma-tile", "mfma", 512, (1, 8, 9, 16, 17), CONV0_MIX),       # both store halves empty, full, and the tile edge
+    ("mfma-block", "mfma", 512, (512, 513), CONV0_MIX),             # second frame block holds one frame
+    ("mfma-exposed", "mfma", 512, (600,), CONV0_EXPOSED),           # exposed regimes of the split and the variance
+    ("mfma-z1", "mfma", 1024, (40,), CONV0_MIX),                    # blockIdx.z = 1
+    ("f32-block", "f32", 512, (63, 64, 65), CONV0_MIX),             # 64-frame apply block edge
+    ("f32-loop", "f32", 1024, (20,), CONV0_MIX),                    # second trip of the channel loop
+    ("f32-idle", "f32", 6, (20,), CONV0_MIX),                       # most threads idle
+    ("f32-exposed", "f32", 512, (600,), CONV0_EXPOSED),
+    ("bf16-apply", "bf16", 64, (65,), ("loud", "dc")),            # bf16 apply path
+    ("stats", "f32", 64, (4096, 4097, 8193), ("plain", "dc")),    # one full statistics block; + one frame; three blocks
+]
+
+
+@functools.lru_cache(maxsize=None)
+def conv0_params(C):
+    """w [C, 10] = 0.3 randn times a power of two per channel (2^-3 .. 2^3), gamma = 1 + 0.1 randn, beta = 0.1 randn."""
+    gen = torch.Generator().manual_seed(4000 + C)
+    w = 0.3 * torch.randn(C, CONV0_K, generator=gen) * torch.pow(2.0, torch.randint(-3, 4, (C, 1), generator=gen).float())
+    return w, 1.0 + 0.1 * torch.randn(C, generator=gen), 0.1 * torch.randn(C, generator=gen)
+
+
+@functools.lru_cache(maxsize=None)
+def conv0_wave(kinds, T0):
+    """[B, nsamp] f32, one utterance per kind; nsamp = (T0 - 1) 5 + 10 + 3: the last three samples reach no frame."""
+    nsamp = (T0 - 1) * CONV0_S + CONV0_K + CONV0_TAIL
+    gen = torch.Generator().manual_seed(77 * T0 + len(kinds))
+    return torch.stack([CONV0_KINDS[k][0] * torch.randn(nsamp, generator=gen) + CONV0_KINDS[k][1] for k in kinds])
+
+
+def conv0_terms64(wave, w):
+    """(y, |x| * |w|) [B, T0, C] float64 on wave's device."""
+    conv = torch.nn.functional.conv1d
+    x, wd = wave.double()[:, None], w.double().to(wave.device)[:, None]
+    return conv(x, wd, stride=CONV0_S).transpose(1, 2), conv(x.abs(), wd.abs(), stride=CONV0_S).transpose(1, 2)
+
+
+def conv0_affine64(y, gamma, beta, eps=CONV0_EPS, unbiased=False):
+    """(mean, var, sc, sh) [B, C] of y [B, T, C]: the GroupNorm with one channel per group, folded."""
+    mean = y.mean(1)
+    var = y.var(1, unbiased=unbiased) if y.shape[1] > 1 else torch.zeros_like(mean)
+    sc = gamma.double().to(y.device) / torch.sqrt(var + eps)
+    return mean, var, sc, beta.double().to(y.device) - mean * sc
+
+
+def conv0_out64(y, ya, sc, sh):
+    r = Conv0Ref()
+    r.y, r.ya, r.sc, r.sh = y, ya, sc, sh
+    r.z = sc[:, None, :] * y + sh[:, None, :]
+    r.s = sc.abs()[:, None, :] * ya + sh.abs()[:, None, :]
+    r.ref = torch.nn.functional.gelu(r.z)
+    r.lin = gelu_grad64(r.z).abs()
+    return r
+
+
+def conv0_ref64(wave, w, gamma, beta):
+    y, ya = conv0_terms64(wave, w)
+    _, _, sc, sh = conv0_affine64(y, gamma, beta)
+    return conv0_out64(y, ya, sc, sh)
+
+
+def conv0_bound(r, path):
+    """Per-element bound of conv0_gn_gelu's output on kernel path "f32" / "bf16" / "mfma"."""
+    if path == "mfma":
+        b = r.lin * (FRONT_C["conv0_split"] * U18) * r.s + GEMM_GELU_BF16OUT_ABS
+    else:
+        b = r.lin * (FRONT_C["conv0_f32"] * U24) * r.s + (GEMM_GELU_ABS if path == "f32" else GEMM_GELU_BF16OUT_ABS)
+    return b if path == "f32" else bf16_round_bound(r.ref, b)
+
+
+def conv0_scsh32(y, gamma, beta):
+    """f32 (sc, sh) as conv0_gn_affine makes them from float64 statistics."""
+    mean, var, _, _ = conv0_affine64(y, gamma, beta)
+    rstd = (1.0 / torch.sqrt(var + float(np.float32(CONV0_EPS)))).float()
+    sc = rstd * gamma.float()
+    return sc, beta.float() - mean.float() * sc
+
+
+def _conv0_frames(wave):
+    T0 = (wave.shape[1] - CONV0_K) // CONV0_S + 1
+    return wave.float().unfold(1, CONV0_K, CONV0_S)[:, :T0]            # [B, T0, K]
+
+
+def conv0_emulate_apply(wave, w, sc, sh):
+    """z as conv0_apply forms it: ten fp32 FMAs in tap order, then fma(y, sc, sh)."""
+    X, wf = _conv0_frames(wave), w.float()
+    y = torch.zeros(X.shape[0], X.shape[1], wf.shape[0])
+    for k in range(CONV0_K):
+        y = _fma32(wf[None, None, :, k], X[:, :, k, None], y)
+    return _fma32(y, sc[:, None, :], sh[:, None, :])
+
+
+def conv0_emulate_mfma(wave, w, sc, sh, drop_xlo=False):
+    """z as conv0_mfma forms it: v = f32(sc w); x, v and sh split into bf16 hi + lo; the 32 products (exact in fp32) of
+    the row [x_hi x_lo x_hi 1 1] . [v_hi v_hi v_lo sh_hi sh_lo] added in order in fp32."""
+    X = _conv0_frames(wave)
+    xh = _bf32(X)
+    xl = _bf32(X - xh)
+    v = sc[:, :, None] * w.float()[None]                               # [B, C, K]
+    vh = _bf32(v)
+    vl = _bf32(v - vh)
+    shh = _bf32(sh)
+    shl = _bf32(sh - shh)
+    acc = torch.zeros(X.shape[0], X.shape[1], v.shape[1])
+    for xa, va in ((xh, vh), (xl, vh), (xh, vl)):
+        if drop_xlo and xa is xl:
+            continue
+        for k in range(CONV0_K):
+            acc = acc + xa[:, :, k, None] * va[:, None, :, k]
+    return (acc + shh[:, None, :]) + shl[:, None, :]
+
+
+# ---- positional conv + GELU
+# (Cg, kp, G, B, S)
+POSCONV_CASES = [
+    (16, 8, 3, 2, 3),       # <1>, single weight stage, S shorter than the padding
+    (16, 16, 2, 2, 257),    # two stages; second block holds one frame
+    (32, 12, 2, 2, 256),    # <2>, three stages, exactly one block
+    (48, 8, 1, 3, 1),       # <3>, S = 1
+    (48, 128, 2, 2, 499),   # the model's group geometry and length, 48 stages, taps straddling stages
+    (64, 2, 2, 2, 255),     # <4>, single stage, kp = 2
+    (64, 128, 2, 2, 300),   # <4>, WavLM-Large group geometry, two blocks
+]
+# Frame scales are 2^-2 .. 2^2 except here. With 128 taps every output has some 2^2 frames in its window, and of
+# K = 8192 one term of a quieter frame is then worth less than the bf16 output's half ulp: over 2^-2 .. 2^2 a dropped
+# (tap, channel) term left the bound on 0.47 - 0.50 of its elements whichever term it was, over 2^-1 .. 2^1 on
+# 0.54 - 0.56 (tests/test_cpu_wavlm_front_ref.py asserts it).
+POSCONV_FS_MAX = {(64, 128, 2, 2, 300): 1}
+
+
+@functools.lru_cache(maxsize=None)
+def posconv_operands(Cg, kp, G, B, S):
+    """x [B, S, E] bf16 = randn times a power of two per frame (2^-2 .. 2^2, POSCONV_FS_MAX); w [E, Cg, kp] bf16 (Conv1d
+    layout) = randn / sqrt(Cg kp) times a power of two per output channel (2^-6 .. 2^6); bias [E] f32 = randn times that scale."""
+    E = G * Cg
+    gen = torch.Generator().manual_seed(100003 * Cg + 1009 * kp + 97 * G + S)
+    fm = POSCONV_FS_MAX.get((Cg, kp, G, B, S), 2)
+    fs = torch.pow(2.0, torch.randint(-fm, fm + 1, (B, S, 1), generator=gen).float())
+    cs = torch.pow(2.0, torch.randint(-6, 7, (E,), generator=gen).float())
+    x = (torch.randn(B, S, E, generator=gen) * fs).to(torch.bfloat16)
+    w = (torch.randn(E, Cg, kp, generator=gen) / (Cg * kp) ** 0.5 * cs[:, None, None]).to(torch.bfloat16)
+    return x, w, torch.randn(E, generator=gen) * cs
+
+
+def posconv_pack(w, G):
+    """Conv1d weight [E, Cg, kp] -> the kernel's [G, Cg, kp * Cg] (tap-major K)."""
+    E, Cg, kp = w.shape
+    return w.view(G, Cg, Cg, kp).permute(0, 1, 3, 2).reshape(G, Cg, kp * Cg).contiguous()
+
+
+def posconv_out64(y, s):
+    r = PosconvRef()
+    r.y, r.s = y, s
+    r.ref = torch.nn.functional.gelu(y)
+    r.lin = gelu_grad64(y).abs()
+    return r
+
+
+def posconv_ref64(x, w, bias, G, device=None):
+    """Float64 reference [B, S, E] on `device`; r.full keeps the S + 1 frames of the padded conv (SamePad drops the last)."""
+    conv = torch.nn.functional.conv1d
+    kp = w.shape[2]
+    xd, wd, bd = (t.to(device).double() for t in (x, w, bias))
+    full = conv(xd.transpose(1, 2), wd, bd, padding=kp // 2, groups=G).transpose(1, 2)
+    s = conv(xd.abs().transpose(1, 2), wd.abs(), bd.abs(), padding=kp // 2, groups=G).transpose(1, 2)[:, :-1]
+    r = posconv_out64(full[:, :-1], s)
+    r.full = full
+    return r
+
+
+def posconv_bound(r):
+    return bf16_round_bound(r.ref, r.lin * (FRONT_C["posconv"] * U24) * r.s + GEMM_GELU_ABS)
+
+
+def posconv_im2col(x, w, G):
+    """Per group (A [B * S, kp * Cg], W [Cg, kp * Cg]) in the operands' dtype, K tap-major as the kernel walks it."""
+    E, Cg, kp = w.shape
+    B, S, _ = x.shape
+    xp = torch.nn.functional.pad(x, (0, 0, kp // 2, kp // 2))
+    win = xp.unfold(1, kp, 1)[:, :S]                                   # [B, S, E, kp]
+    Wp = posconv_pack(w, G)
+    return [(win[:, :, g * Cg:(g + 1) * Cg].permute(0, 1, 3, 2).reshape(B * S, kp * Cg), Wp[g]) for g in range(G)]
+
+
+def posconv_emulate(x, w, bias, G):
+    """fp32 in the kernel's order: 32-wide K chunks (one MFMA each, products of two bf16 exact) added in order, then the
+    bias. [B, S, E] float32."""
+    B, S, E = x.shape
+    cols = []
+    for A, Wg in posconv_im2col(x, w, G):
+        A, Wg = A.float(), Wg.float()
+        acc = torch.zeros(A.shape[0], Wg.shape[0])
+        for k in range(0, A.shape[1], 32):
+            acc = acc + A[:, k:k + 32] @ Wg[:, k:k + 32].t()
+        cols.append(acc)
+    return (torch.cat(cols, 1) + bias.float()[None, :]).view(B, S, E)
+
+
+# ---- gated relative-position gate
+# (dtype, B, S, H, dh)
+GATE_CASES = [
+    ("f32", 2, 100, 3, 64),     # 600 entries, three blocks, the last ragged
+    ("bf16", 2, 100, 3, 64),    # H not a power of two: e / H and e % H matter
+    ("bf16", 3, 43, 5, 32),     # narrower head
+    ("f32", 1, 7, 2, 8),        # one partial block, the narrowest head
+    ("bf16", 2, 128, 1, 64),    # exactly one full block
+]
+
+
+@functools.lru_cache(maxsize=None)
+def gate_operands(dt, B, S, H, dh):
+    """x [B * S, H dh] randn (rounded to bf16 for "bf16"), W [8, dh] = 0.2 randn times a power of two per row
+    (2^-2 .. 2^2), bias = 0.5 randn, cst = 0.5 + rand, distinct per head."""
+    gen = torch.Generator().manual_seed(7919 * B + 131 * S + 17 * H + dh + (dt == "bf16"))
+    x = torch.randn(B * S, H * dh, generator=gen).to(torch.bfloat16 if dt == "bf16" else torch.float32)
+    W = 0.2 * torch.randn(8, dh, generator=gen) * torch.pow(2.0, torch.randint(-2, 3, (8, 1), generator=gen).float())
+    return x, W, 0.5 * torch.randn(8, generator=gen), 0.5 + torch.rand(H, generator=gen)
+
+
+def gate_out64(p, sp, cst):
+    """p, sp [B, S, H, 8] float64 (pre-activations and their error scales), cst [H] -> GateRef with ref [B, H, S]."""
+    r = GateRef()
+    c = cst.double().to(p.device)[None, None, :]
+    r.pa, r.pb = p[..., :4].sum(-1), p[..., 4:].sum(-1)
+    r.sa, r.sb = sp[..., :4].sum(-1), sp[..., 4:].sum(-1)
+    ga, gb = torch.sigmoid(r.pa), torch.sigmoid(r.pb)
+    r.ref = (ga * (gb * c - 1.0) + 2.0).transpose(1, 2)
+    r.da = (ga * (1 - ga) * (gb * c - 1.0)).abs()
+    r.db = (ga * c * gb * (1 - gb)).abs()
+    # fast exp: (|p| + 4) u relative on e^-p through sigma (1 - sigma); then the closing arithmetic
+    r.A = U24 * ((r.pa.abs() + 4) * r.da + (r.pb.abs() + 4) * r.db + 4 * ((ga * gb * c).abs() + ga.abs() + 2.0))
+    return r
+
+
+def gate_ref64(x, W, bias, cst, B, S, H):
+    xh = x.double().view(B, S, H, -1)
+    Wd, bd = W.double().to(x.device), bias.double().to(x.device)
+    return gate_out64(xh @ Wd.t() + bd, xh.abs() @ Wd.abs().t() + bd.abs(), cst)
+
+
+def gate_bound(r, C=None):
+    """[B, H, S], laid out as the output."""
+    C = FRONT_C["gate"] if C is None else C
+    return ((r.da * r.sa + r.db * r.sb) * (C * U24) + r.A).transpose(1, 2)
+
+
+def gate_emulate(x, W, bias, cst, B, S, H):
+    """fp32 in the kernel's order: per output, fma over the head's channels in order starting from the bias; the two
+    sums of four; torch.exp in fp32. Returns (pa, pb [B, S, H], gate [B, H, S]) float32."""
+    xh, Wf = x.float().view(B, S, H, -1), W.float()
+    r = bias.float().expand(B, S, H, 8).contiguous()
+    for d in range(xh.shape[-1]):
+        r = _fma32(Wf[:, d], xh[..., d, None], r)
+    pa = ((r[..., 0] + r[..., 1]) + r[..., 2]) + r[..., 3]
+    pb = ((r[..., 4] + r[..., 5]) + r[..., 6]) + r[..., 7]
+    ga, gb = 1.0 / (1.0 + torch.exp(-pa)), 1.0 / (1.0 + torch.exp(-pb))
+    return pa, pb, (ga * (gb * cst.float()[None, None, :] - 1.0) + 2.0).transpose(1, 2)
