@@ -35,8 +35,9 @@ struct GemmArgs {
 __device__ __forceinline__ int swz_kc(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
 
 // 256x256 8-phase bf16 NT GEMM (gemm256.hip). Preconditions: bf16 A/B, both K-contiguous, K % 64 == 0,
-// 16-B aligned rows, N % 8 == 0, conv without padding taps and Cg % 64 == 0. epi: STORE, GELU, GELU_ONLY;
-// out_dtype: FDDM_BF16 or FDDM_F32 (STORE only). Returns hipError_t.
+// 16-B aligned rows, N % 8 == 0, conv without padding taps and Cg % 64 == 0. epi: STORE, GELU, GELU_ONLY, DGELU
+// (bf16, C2 = the saved pre-activation, not C itself); out_dtype: FDDM_BF16 or FDDM_F32 (STORE, and ACC_F32
+// without a bias). Returns hipError_t.
 int gemm256_launch(const GemmArgs& g, int epi, int out_dtype, bool conv, hipStream_t s);
 bool gemm256_ok(const GemmArgs& g, int epi, int out_dtype, bool conv);
 long gemm256_tiles(long M, long N);

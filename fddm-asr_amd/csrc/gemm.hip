@@ -7,7 +7,8 @@
 //                                                 implicit GEMM: the A row of output frame t is the
 //                                                 window x[s*t .. s*t+k) of a channels-last input,
 //                                                 i.e. lda = s*C < K, overlapping rows)
-//   backward dX = dY W   : A=dY KC, B=W  MC
+//   backward dX = dY W   : A=dY KC, B=W  MC        (the decoder block backward passes a transposed bf16 copy W^T instead,
+//                                                 A=dY KC, B=W^T KC, so that the 256x256 kernel can take it)
 //   backward dW = dY^T X : A=dY MC, B=X  MC
 // A rows are batched for the conv case: A(m,k) at A + (m / Mi)*sAb + (m % Mi)*lda + k.
 //
@@ -758,8 +759,10 @@ FDDM_API int fddm_gemm(int dtype, int a_dtype, int a_kc, int b_kc, int epi, int 
   const long t128 = gemm128_tiles(M, N);
   const bool split128 = out_dtype == FDDM_F32 && (epi == EPI_STORE || epi == EPI_ACC_F32) && t128 < 192 && K >= 4096;
   const bool bias_acc128 = bias && (epi == EPI_ACC_F32 || split128);
-  if (dtype == FDDM_BF16 && a_dtype == FDDM_BF16 && Mi >= M && g128_enabled() && !bias_acc128 &&
-      !(a_kc && b_kc && !colsum && g256_enabled() && gemm256_ok(g, epi, out_dtype, false) && prefer_256(M, N)) &&
+  // the 256x256 kernel's choice, made once: NT, its preconditions, enough tiles (prefer_256)
+  const bool to256 = dtype == FDDM_BF16 && a_dtype == FDDM_BF16 && a_kc && b_kc && Mi >= M && !colsum && g256_enabled() &&
+                     gemm256_ok(g, epi, out_dtype, false) && prefer_256(M, N);
+  if (dtype == FDDM_BF16 && a_dtype == FDDM_BF16 && Mi >= M && g128_enabled() && !bias_acc128 && !to256 &&
       gemm128_ok(g, a_kc, b_kc, epi, out_dtype) && (!colsum || !a_kc)) {
     int nz128 = 1;
     if (split128) {
@@ -784,7 +787,9 @@ FDDM_API int fddm_gemm(int dtype, int a_dtype, int a_kc, int b_kc, int epi, int 
   int nz = 1;
   const long tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
   const int kstep = dtype == FDDM_BF16 ? 64 : 32;
-  if (out_dtype == FDDM_F32 && (epi == EPI_STORE || epi == EPI_ACC_F32) && tiles < 512 && K >= 8 * kstep && Mi >= M) {
+  // (an accumulate the 256x256 kernel takes is not split: its epilogue adds in place, with no atomics)
+  if (out_dtype == FDDM_F32 && (epi == EPI_STORE || epi == EPI_ACC_F32) && tiles < 512 && K >= 8 * kstep && Mi >= M &&
+      !(to256 && epi == EPI_ACC_F32)) {
     // Split count: enough workgroups to cover the chip (splitk_target), but every split keeps at least
     // splitk_mink of K — each extra split costs M*N*4 B of float atomics (~1.3 TB/s chip-wide).
     long want = (splitk_target() + tiles - 1) / tiles;
@@ -802,8 +807,7 @@ FDDM_API int fddm_gemm(int dtype, int a_dtype, int a_kc, int b_kc, int epi, int 
       }
     }
   }
-  if (dtype == FDDM_BF16 && a_dtype == FDDM_BF16 && a_kc && b_kc && nz == 1 && Mi >= M && !colsum &&
-      g256_enabled() && gemm256_ok(g, epi, out_dtype, false) && prefer_256(M, N)) {
+  if (to256 && nz == 1) {
     note_path(LP_256, 1);
     return gemm256_launch(g, epi, out_dtype, false, s);
   }

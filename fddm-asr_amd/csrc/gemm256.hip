@@ -26,6 +26,19 @@
 // (DMA, bias loads, stores — all explicit, none compiler-generated) and waits for "issued since X".
 // The MFMAs compute C^T fragments (operands swapped) so a lane owns 4 consecutive columns of one row: the
 // epilogue writes 16-B buffer stores of whole 128-B lines from the accumulators after two lane exchanges.
+//
+// Two epilogues read as well (the decoder's input gradients dY Wt against the transposed weight copies):
+//   EPI_ACC_F32  C += A B^T (no bias). A tile's previous C is loaded straight into its accumulators — 32 16-B loads
+//     per lane, in the prologue for a workgroup's first tile and in the EP phase 1 for every later one, each row
+//     block right after the finished tile's stores of that block — so the MFMAs add onto it and the epilogue is the
+//     f32 store. Vector-memory accounting: the prologue loads are older than everything its first wait counts; in
+//     EP phase 1 they are the youngest instructions and the MFMAs of that phase need them, so the phase ends in
+//     vmcnt(0) and phases 2-4 use the steady counts. A shifted tile masks the stores of the rows / columns it
+//     shares with its neighbour (an addition is not idempotent); no count of this build includes a store.
+//   EPI_DGELU    C = acc gelu'(C2) keep scale, bf16. C2 is loaded in the epilogue, DG_D row blocks ahead of its
+//     use, behind exact counts (dgelu_wait); all 32 loads have landed when the last row block is stored, so phases
+//     2-4 of the EP K-tile count the 16 stores exactly as the STORE build does (fewer in flight than counted only
+//     makes a wait stricter). A shifted tile recomputes its neighbour's values bit for bit, as in the STORE build.
 #include "gemm.h"
 #include <type_traits>
 
@@ -83,6 +96,40 @@ __device__ __forceinline__ void store16(const u32x4_t& d, const i32x4_t& srd, in
 #endif
   asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" ::"v"(d), "v"(voff), "s"(srd), "s"(soff)
                : "memory");
+}
+// 16-B buffer load as inline asm (EPI_ACC_F32 reads the previous C): hipcc must not count it, the kernel waits for
+// it with its own vmcnt before the first use of the result
+__device__ __forceinline__ f32x4_t load16(const i32x4_t& srd, int voff, int soff) {
+  f32x4_t v;
+  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=&v"(v) : "v"(voff), "s"(srd), "s"(soff) : "memory");
+  return v;
+}
+__device__ __forceinline__ u32x2_t load8(const i32x4_t& srd, int voff, int soff) {
+  u32x2_t v;
+  asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "=&v"(v) : "v"(voff), "s"(srd), "s"(soff) : "memory");
+  return v;
+}
+// EPI_DGELU epilogue: younger vector-memory instructions at the wait for the pre-activation loads L(i) of row block
+// i, the loads running D = DG_D row blocks ahead. Issue order: L(0) .. L(D-1), then per row block k = 0..7: wait(k),
+// its 2 stores S(k), L(k+D) while k + D < 8; every L is 4 instructions. After L(i), i < D: L(i+1 .. D-1) and S(k),
+// L(k+D) for k < i = 4 (D - 1 - i) + 6 i. After L(i), i >= D (issued behind S(i-D)): S(i-D+1 .. i-1) = 2 (D - 1) and
+// the loads L(k+D) with i-D+1 <= k <= min(i-1, 7-D) = 4 min(D - 1, 7 - i).
+// (D = 4 spilled: 256 VGPRs and 64 B of scratch per lane, which no counted wait would know about.)
+constexpr int DG_D = 2;
+constexpr int dgelu_wait(int i) {
+  return i < DG_D ? 4 * (DG_D - 1 - i) + 6 * i : 2 * (DG_D - 1) + 4 * (DG_D - 1 < 7 - i ? DG_D - 1 : 7 - i);
+}
+__device__ __forceinline__ void dgelu_vmcnt(int i) {  // i is an unrolled loop's counter: one case survives
+  switch (i) {
+    case 0: vmcnt<dgelu_wait(0)>(); break;
+    case 1: vmcnt<dgelu_wait(1)>(); break;
+    case 2: vmcnt<dgelu_wait(2)>(); break;
+    case 3: vmcnt<dgelu_wait(3)>(); break;
+    case 4: vmcnt<dgelu_wait(4)>(); break;
+    case 5: vmcnt<dgelu_wait(5)>(); break;
+    case 6: vmcnt<dgelu_wait(6)>(); break;
+    default: vmcnt<dgelu_wait(7)>(); break;
+  }
 }
 __device__ __forceinline__ i32x4_t make_srd(const void* base) {
   const unsigned long a = (unsigned long)base;
@@ -205,6 +252,20 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
   int cm0, cn0, nm0, nn0;
   coords(0, cm0, cn0);
   coords(1, nm0, nn0);
+  // EPI_ACC_F32 must add a product to each element once: a shifted (ragged last) tile leaves the rows / columns it
+  // shares with its neighbour to that neighbour. (dm, dn) = how far the tile was shifted = the rows / columns it skips.
+  constexpr bool ACC = EPI == EPI_ACC_F32;
+  auto shifts = [&](int i, int m0, int n0, int& dm, int& dn) {
+    const int s = s0 + jx + min(i, nmine - 1) * Px;
+    const int per = GM * nN, grp = s / per, first = grp * GM, gsz = min(GM, nM - first), rr = s - grp * per;
+    dm = (first + rr % gsz) * BM - m0;
+    dn = (rr / gsz) * BN - n0;
+  };
+  int cdm = 0, cdn = 0, ndm = 0, ndn = 0, edm = 0, edn = 0;  // current / next / finished tile
+  if constexpr (ACC) {
+    shifts(0, cm0, cn0, cdm, cdn);
+    shifts(1, nm0, nn0, ndm, ndn);
+  }
   if (CONV) {
     conv_rows(vcc, cm0);
     conv_rows(vcn, nm0);
@@ -247,7 +308,7 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
   // ---------------------------------------------------------------- stores
   // buffer stores: lane offset fixed, tile origin and block offset in soffset
   const i32x4_t rc = make_srd(g.C);
-  const i32x4_t rc2 = make_srd(EPI == EPI_GELU ? g.C2 : g.C);
+  const i32x4_t rc2 = make_srd(EPI == EPI_GELU || EPI == EPI_DGELU ? g.C2 : g.C);
   constexpr int ESZ = (int)sizeof(OT);
   // store instructions per half (4 row blocks x 64 columns): f32 16; bf16 8 per output
   constexpr int SPH = sizeof(OT) == 4 ? 16 : (EPI == EPI_GELU ? 16 : 8);
@@ -262,6 +323,12 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
   const int cc = sizeof(OT) == 4 ? 4 * fg : 4 * fg + ((fg & 1) ? 12 : 0);
   const int vst = ((wr * 128 + (fr & ~1)) * ldc + wc * 64 + (fr & 1) * (sizeof(OT) == 4 ? 16 : 32) + cc) * ESZ;
   const bool odd_r = fr & 1;
+  // EPI_ACC_F32: the previous C of a tile seeds its accumulators where the other builds seed the bias, one 16-B
+  // buffer load per 16x16 block in the accumulator layout (acc[i][j][e] = row wr*128 + i*16 + fr, column
+  // wc*64 + j*16 + 4*fg + e). srow / scol: the row / first column within the tile of this lane's first store.
+  // EPI_DGELU loads the saved bf16 pre-activation in the same layout (8 B per block).
+  const int vld = ((wr * 128 + fr) * ldc + wc * 64 + 4 * fg) * ESZ;
+  const int srow = wr * 128 + (fr & ~1), scol = wc * 64 + (fr & 1) * 16 + 4 * fg;
 
   u32x4_t af[4][2], b0[2][2], b1[2][2];
   f32x4_t acc[8][4];
@@ -304,14 +371,47 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
   auto epi_rows = [&](auto ibc, auto nc, int em0, int en0, bool reseed) {
     constexpr int ib = decltype(ibc)::value, NR = decltype(nc)::value;
     f32x4_t bq[4];
-    if (reseed) {
-      bias_pair(0, bq[0], bq[1]);
-      bias_pair(2, bq[2], bq[3]);
+    if constexpr (!ACC) {
+      if (reseed) {
+        bias_pair(0, bq[0], bq[1]);
+        bias_pair(2, bq[2], bq[3]);
+      }
+    }
+    // EPI_DGELU: the saved bf16 pre-activation of the finished tile in the accumulator layout (4 consecutive
+    // columns = 8 B per block), loaded DG_D row blocks ahead into a ring of DG_D x 4 register pairs
+    u32x2_t pre[DG_D][4];
+    auto load_pre = [&](int i) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        pre[i % DG_D][j] = load8(rc2, vld, ((em0 + i * 16) * ldc + en0 + j * 16) * ESZ);
+    };
+    if constexpr (EPI == EPI_DGELU) {
+      static_assert(EPI != EPI_DGELU || (ib == 0 && NR == 8), "dgelu_wait counts a whole tile");
+#pragma unroll
+      for (int i = 0; i < DG_D; ++i) load_pre(i);
     }
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
       const int so = ((em0 + (ib + i) * 16) * ldc + en0) * ESZ;
-      if constexpr (sizeof(OT) == 4) {
+      if constexpr (ACC) {
+        // acc = previous C + product. Lanes in the rows / columns a shifted tile shares with its neighbour store
+        // nothing (a wave whose lanes are all masked may skip the instruction: no wait of this build counts stores)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          u32x4_t x0 = __builtin_bit_cast(u32x4_t, acc[ib + i][2 * p]);
+          u32x4_t x1 = __builtin_bit_cast(u32x4_t, acc[ib + i][2 * p + 1]);
+          xchg1(x0, x1);
+          const bool cok = scol + 32 * p >= edn;
+          const int r = srow + (ib + i) * 16;
+          if (cok && r >= edm) store16(x0, rc, vst, so + 32 * p * ESZ);
+          if (cok && r + 1 >= edm) store16(x1, rc, vst, so + (ldc + 32 * p) * ESZ);
+        }
+        if (reseed) {  // this row block of the tile now running (cm0, cn0)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[ib + i][j] = load16(rc, vld, ((cm0 + (ib + i) * 16) * ldc + cn0 + j * 16) * ESZ);
+        }
+      } else if constexpr (sizeof(OT) == 4) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
           u32x4_t x0 = __builtin_bit_cast(u32x4_t, acc[ib + i][2 * p]);
@@ -340,6 +440,30 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
             }
           }
           emit_bf16(v, rc2, so);
+        } else if constexpr (EPI == EPI_DGELU) {
+          // C = acc gelu'(pre) keep scale: the keep bits of the forward's GELU epilogue (same element index)
+          dgelu_vmcnt(i);
+          asm volatile("" : "+v"(pre[i % DG_D][0]), "+v"(pre[i % DG_D][1]), "+v"(pre[i % DG_D][2]), "+v"(pre[i % DG_D][3]));
+          const unsigned thr = g.thr16;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            unsigned keep = 0xfu;
+            if (thr) {
+              const unsigned m = (unsigned)(em0 + wr * 128 + (ib + i) * 16 + fr);
+              const unsigned n = (unsigned)(en0 + wc * 64 + j * 16 + 4 * fg);
+              keep = drop_keep4(eff_seed(g.seed, g.seed_off), g.stream, ((uint64_t)m * (uint64_t)Nc + n) >> 2, thr);
+            }
+            const u32x2_t pu = pre[i % DG_D][j];
+            const float pv[4] = {__uint_as_float(pu[0] << 16), __uint_as_float(pu[0] & 0xffff0000u),
+                                 __uint_as_float(pu[1] << 16), __uint_as_float(pu[1] & 0xffff0000u)};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float a = v[j][e] * gelu_grad(pv[e]);
+              v[j][e] = (keep >> e) & 1u ? (thr ? a * g.drop_scale : a) : 0.f;
+            }
+          }
+          emit_bf16(v, rc, so);
+          if (i + DG_D < NR) load_pre(i + DG_D);
         } else {
           if constexpr (EPI == EPI_GELU_ONLY) {  // the frozen encoder's conv layers / FF1: bf16-output GELU
 #pragma unroll
@@ -350,9 +474,11 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
           emit_bf16(v, rc, so);
         }
       }
-      if (reseed) {
+      if constexpr (!ACC) {
+        if (reseed) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[ib + i][j] = bq[j];
+          for (int j = 0; j < 4; ++j) acc[ib + i][j] = bq[j];
+        }
       }
       __builtin_amdgcn_sched_barrier(0);  // one row block at a time: bounds the epilogue's live registers
     }
@@ -429,7 +555,14 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
 
   // ---------------------------------------------------------------- prologue
   // VMEM issue order (= the steady-state order of the K loop): bias(tile 0), A0 B0 B1 A1 of K-tile 0,
-  // A0 B0 of K-tile 1
+  // A0 B0 of K-tile 1. EPI_ACC_F32 issues the 32 loads of tile 0's previous C ahead of them all: the first wait below
+  // counts from the bias DMA on, so it covers every older instruction as well.
+  if constexpr (ACC) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = load16(rc, vld, ((cm0 + i * 16) * ldc + cn0 + j * 16) * ESZ);
+  }
   load_bias(cn0, true);
   {
     const int kt1 = 1 % nk;
@@ -443,14 +576,20 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
   }
   vmcnt<8>();  // bias(0), A0(0), B0(0) landed
   bar();
+  if constexpr (ACC) {
 #pragma unroll
-  for (int jb = 0; jb < 4; jb += 2) {
-    f32x4_t v0, v1;
-    bias_pair(jb, v0, v1);
+    for (int i = 0; i < 8; ++i)  // loaded above, landed by the wait: the compiler may touch them from here on
+      asm volatile("" : "+v"(acc[i][0]), "+v"(acc[i][1]), "+v"(acc[i][2]), "+v"(acc[i][3]));
+  } else {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      acc[i][jb] = v0;
-      acc[i][jb + 1] = v1;
+    for (int jb = 0; jb < 4; jb += 2) {
+      f32x4_t v0, v1;
+      bias_pair(jb, v0, v1);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        acc[i][jb] = v0;
+        acc[i][jb + 1] = v1;
+      }
     }
   }
   readB(0, IC<HB0>{}, b0);
@@ -475,6 +614,8 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
 #else
   constexpr int D2 = 0;
 #endif
+  // stores of an EP K-tile's phase 1 that phases 2-4 may still find in flight (EPI_ACC_F32: none, see phase 1)
+  constexpr int EPS = ACC ? 0 : 2 * SPH;
   auto ktile = [&](int T, bool EP) {
     const int bc = T & 1, bn = bc ^ 1;
     // K-tile T+1 is in the next tile iff LAST; T+2 iff kt >= nk-2
@@ -490,23 +631,35 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
     // counts: VMEM instructions issued after the awaited half's second (pending) instruction
     vmcnt<8 - D2>();  // B1(T)
     if (EP) epi_rows(IC<0>{}, IC<8>{}, em0, en0, true);
+    // EPI_ACC_F32: the epilogue's 32 loads of the next C seed the accumulators the MFMAs below add to, and they are
+    // the youngest vector-memory instructions of the wave, so the wait is for everything: vmcnt(0), whatever number
+    // of masked stores was skipped. Both LDS-DMA instructions of this phase come after it (inside mma), so phases
+    // 2-4 of an EP K-tile then see exactly the steady counts: EPS = 0 stores in flight.
+    if constexpr (ACC) {
+      if (EP) {
+        vmcnt<0>();
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          asm volatile("" : "+v"(acc[i][0]), "+v"(acc[i][1]), "+v"(acc[i][2]), "+v"(acc[i][3]));
+      }
+    }
     mma(0, 0, b0);
     // ---- phase 2: A rows 0..63 x B cols 32..63
     readB(bc, IC<HB1>{}, b1);
     if (CONV) issueA(HA1, bn, kt1, m1, n1b ? vcn : vcc, true);
     else issueA(HA1, bn, kt1, m1, vcc, true);
-    wait2(EP, IC<8 - D2>{}, IC<8 - D2 + 2 * SPH>{});  // A1(T)
+    wait2(EP, IC<8 - D2>{}, IC<8 - D2 + EPS>{});  // A1(T)
     mma(0, 2, b1);
     // ---- phase 3: A rows 64..127 x B cols 0..31
     readA(bc, IC<HA1>{});
     if (CONV) issueA(HA0, bc, kt2, m2, n2 ? vcn : vcc, true);
     else issueA(HA0, bc, kt2, m2, vcc, true);
-    wait2(EP, IC<6 - D2>{}, IC<6 - D2 + 2 * SPH>{});  // B0(T+1)
+    wait2(EP, IC<6 - D2>{}, IC<6 - D2 + EPS>{});  // B0(T+1)
     mma(4, 0, b0);
     // ---- phase 4: A rows 64..127 x B cols 32..63; B0 fragments of K-tile T+1
     readB(bn, IC<HB0>{}, b0);
     issueB(HB0, bc, kt2, n2c, true);
-    wait2(EP, IC<10 - D2>{}, IC<10 - D2 + 2 * SPH>{});  // A0(T+1)
+    wait2(EP, IC<10 - D2>{}, IC<10 - D2 + EPS>{});  // A0(T+1)
     mma(4, 2, b1);
   };
   // after a tile's last K-tile: its results move to the epilogue slot, the workgroup's next tile becomes current
@@ -516,6 +669,13 @@ __global__ void __launch_bounds__(512) gemm256_kernel(GemmArgs g) {
     cm0 = nm0;
     cn0 = nn0;
     coords(ti + 2, nm0, nn0);
+    if constexpr (ACC) {
+      edm = cdm;
+      edn = cdn;
+      cdm = ndm;
+      cdn = ndn;
+      shifts(ti + 2, nm0, nn0, ndm, ndn);
+    }
     if (CONV) {
 #pragma unroll
       for (int h = 0; h < 2; ++h)
@@ -590,18 +750,22 @@ bool gemm256_ok(const GemmArgs& g, int epi, int out_dtype, bool conv) {
   const long esz = out_dtype == FDDM_F32 ? 4 : 2;
   if (((g.M - 1) * g.ldc + g.N) * esz >= (1L << 31)) return false;  // 32-bit buffer offsets
   if (conv && (g.geo.cpad != 0 || g.geo.Cg % 64 || ((g.geo.Cg / 64) & (g.geo.Cg / 64 - 1)))) return false;
-  if (out_dtype == FDDM_F32) return epi == EPI_STORE && !conv;
+  // the accumulate epilogue seeds the accumulators with C where the others seed the bias: no bias, as on gemm128
+  if (out_dtype == FDDM_F32) return (epi == EPI_STORE || (epi == EPI_ACC_F32 && !g.bias)) && !conv;
   if (conv) return epi == EPI_STORE || epi == EPI_GELU_ONLY;
+  if (epi == EPI_DGELU) return g.C2 != nullptr && g.C2 != g.C;  // a shifted tile reads C2 again after its neighbour's stores
   return epi == EPI_STORE || epi == EPI_GELU || epi == EPI_GELU_ONLY;
 }
 
 int gemm256_launch(const GemmArgs& g, int epi, int out_dtype, bool conv, hipStream_t s) {
   if (!gemm256_ok(g, epi, out_dtype, conv)) return (int)hipErrorInvalidValue;
-  if (out_dtype == FDDM_F32) return g256::launch<EPI_STORE, float, false>(g, s);
+  if (out_dtype == FDDM_F32)
+    return epi == EPI_ACC_F32 ? g256::launch<EPI_ACC_F32, float, false>(g, s) : g256::launch<EPI_STORE, float, false>(g, s);
   if (conv) {
     if (epi == EPI_GELU_ONLY) return g256::launch<EPI_GELU_ONLY, bf16_t, true>(g, s);
     return g256::launch<EPI_STORE, bf16_t, true>(g, s);
   }
+  if (epi == EPI_DGELU) return g256::launch<EPI_DGELU, bf16_t, false>(g, s);
   if (epi == EPI_GELU) return g256::launch<EPI_GELU, bf16_t, false>(g, s);
   if (epi == EPI_GELU_ONLY) return g256::launch<EPI_GELU_ONLY, bf16_t, false>(g, s);
   return g256::launch<EPI_STORE, bf16_t, false>(g, s);

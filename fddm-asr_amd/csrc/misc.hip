@@ -232,6 +232,45 @@ __global__ void cast_bf16_f32_kernel(const bf16_t* __restrict__ x, float* __rest
   if (i < n) y[i] = bf2f(x[i]);
 }
 
+// Multi-tensor bf16 transpose dst[c][r] = src[r][c] (src [rows][cols], dst [cols][rows], both contiguous, rows and
+// cols multiples of 8, 16-B aligned): the K-contiguous weight copies W^T the decoder's input-gradient GEMMs read.
+// tab[5 t + 0..4] = src, dst, rows, cols, first workgroup of tensor t; a workgroup moves one 64x64 tile through LDS:
+// 16-B global loads along cols (8 lanes = one 128-B row segment), 2-byte LDS writes into the transposed image
+// (row stride 72 elements = 144 B, so its 16-B chunks stay aligned), 16-B LDS reads and 16-B global stores along rows.
+constexpr int TR_T = 64, TR_LD = 72;
+__global__ void __launch_bounds__(256) transpose_bf16_mt_kernel(const long* __restrict__ tab, int nt) {
+  __shared__ __attribute__((aligned(16))) unsigned short img[TR_T * TR_LD];
+  const int b = blockIdx.x;
+  int t = 0;
+  while (t + 1 < nt && b >= tab[5 * (t + 1) + 4]) ++t;
+  const unsigned short* src = (const unsigned short*)tab[5 * t];
+  unsigned short* dst = (unsigned short*)tab[5 * t + 1];
+  const long rows = tab[5 * t + 2], cols = tab[5 * t + 3];
+  const long local = b - tab[5 * t + 4], tc = (cols + TR_T - 1) / TR_T;
+  if (local >= tc * ((rows + TR_T - 1) / TR_T)) return;  // (workgroup-uniform)
+  const long r0 = (local / tc) * TR_T, c0 = (local % tc) * TR_T;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int q = threadIdx.x + 256 * i, r = q >> 3, c = (q & 7) * 8;
+    if (r0 + r < rows && c0 + c < cols) {  // whole chunk inside: cols % 8 == 0
+      const uint4 u = *(const uint4*)(src + (r0 + r) * cols + c0 + c);
+      const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        img[(c + 2 * e) * TR_LD + r] = (unsigned short)(w[e] & 0xffffu);
+        img[(c + 2 * e + 1) * TR_LD + r] = (unsigned short)(w[e] >> 16);
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int q = threadIdx.x + 256 * i, c = q >> 3, r = (q & 7) * 8;
+    if (c0 + c < cols && r0 + r < rows)  // whole chunk inside: rows % 8 == 0
+      *(uint4*)(dst + (c0 + c) * rows + r0 + r) = *(const uint4*)(img + c * TR_LD + r);
+  }
+}
+
 }  // namespace fddm
 
 using namespace fddm;
@@ -332,6 +371,13 @@ FDDM_API int fddm_cast(int src_dtype, int dst_dtype, const void* x, void* y, lon
     hipLaunchKernelGGL(cast_bf16_f32_kernel, g1(n), dim3(256), 0, (hipStream_t)hs, (const bf16_t*)x, (float*)y, n);
   else
     return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
+FDDM_API int fddm_transpose_bf16_mt(const long* table, long ntensors, long nblocks, void* hs) {
+  if (ntensors <= 0 || nblocks <= 0) return 0;
+  if (!table || ntensors > (1L << 20) || nblocks > (1L << 30)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(transpose_bf16_mt_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)hs, table, (int)ntensors);
   return (int)hipGetLastError();
 }
 

@@ -313,6 +313,11 @@ class DecoderBlockFn(torch.autograd.Function):
         cd = rt.compute_dtype()
         W = {k: rt.wt(v_) for k, v_ in (("sa", sa_w), ("so", so_w), ("ca", ca_w), ("co", co_w), ("f0", f0_w),
                                          ("f3", f3_w))}
+        # transposed bf16 copies [in, out] (None in fp32 mode): the input-gradient GEMMs below read them as ordinary
+        # K-contiguous operands, which opens the 256x256 kernel to them (ops.linear_dx wt=)
+        WT = {k: rt.wt_t(v_) for k, v_ in (("sa", sa_w), ("so", so_w), ("ca", ca_w), ("co", co_w), ("f0", f0_w),
+                                           ("f3", f3_w))}
+        cols = lambda t, a, b: None if t is None else t[:, a:b]     # noqa: E731  (rows a..b of W = columns of W^T)
         # gradient destinations: arena views (accumulated in place) or fresh tensors
         # (every destination accumulates: the weight gradients are deferred to one grouped launch at the end)
         G = [_gdst(p_, zero=True) for p_ in params]
@@ -331,9 +336,10 @@ class DecoderBlockFn(torch.autograd.Function):
         dw_jobs = [(dy3, hact, gf3_w, gf3_b)]
         FF = f0_w.shape[0]
         dh = torch.empty(N, FF, device=dev, dtype=cd)
-        ops.linear_dx(dy3, W["f3"], out=dh, epi=ops.EPI_DGELU, C2=hpre, drop_p=p, seed=seed, rng_stream=st + 5)
+        ops.linear_dx(dy3, W["f3"], out=dh, epi=ops.EPI_DGELU, C2=hpre, drop_p=p, seed=seed, rng_stream=st + 5,
+                      wt=WT["f3"])
         dw_jobs.append((dh, x2T, gf0_w, gf0_b))
-        ops.linear_dx(dh, W["f0"], out=dx2, accumulate=True)
+        ops.linear_dx(dh, W["f0"], out=dx2, accumulate=True, wt=WT["f0"])
         # LN2 + FiLM
         dx1 = torch.empty(N, d, device=dev, dtype=F32)
         dyc = torch.empty(N, d, device=dev, dtype=cd)
@@ -346,7 +352,7 @@ class DecoderBlockFn(torch.autograd.Function):
                    dfilm=(dfs, dfh), rows_per_batch=L, drop_p=p, seed=seed, rng_stream=st + 4, partials=lnp)
         # cross out-proj + attention
         dw_jobs.append((dyc, oc, gco_w, gco_b))
-        doc = ops.linear_dx(dyc, W["co"], out_dtype=cd)
+        doc = ops.linear_dx(dyc, W["co"], out_dtype=cd, wt=WT["co"])
         dqc = torch.empty(N, d, device=dev, dtype=cd)
         dkvc = torch.empty(B * S, 2 * d, device=dev, dtype=cd)
         bits_s, bits_c = ctx.bits
@@ -358,7 +364,7 @@ class DecoderBlockFn(torch.autograd.Function):
         with rt.probe("decoder.cross_attn_bwd", replay=bwd_c):
             bwd_c()
         dw_jobs += [(dqc, x1T, gca_w[:d], gca_b[:d]), (dkvc, cT, gca_w[d:], gca_b[d:])]
-        ops.linear_dx(dqc, W["ca"][:d], out=dx1, accumulate=True)
+        ops.linear_dx(dqc, W["ca"][:d], out=dx1, accumulate=True, wt=cols(WT["ca"], 0, d))
         # LN1
         dx = torch.empty(N, d, device=dev, dtype=F32)
         dy = torch.empty(N, d, device=dev, dtype=cd)
@@ -366,7 +372,7 @@ class DecoderBlockFn(torch.autograd.Function):
                    rng_stream=st + 2, partials=lnp)
         # self out-proj + attention
         dw_jobs.append((dy, o, gso_w, gso_b))
-        do = ops.linear_dx(dy, W["so"], out_dtype=cd)
+        do = ops.linear_dx(dy, W["so"], out_dtype=cd, wt=WT["so"])
         dqk = torch.empty(N, 2 * d, device=dev, dtype=cd)
         dv = torch.empty(N, d, device=dev, dtype=cd)
         bwd_s = lambda: ops.attn_bwd(qk, qk[:, d:], v, o, do, lse, dqk, dqk[:, d:], dv, B, H, L, L,  # noqa: E731
@@ -374,7 +380,7 @@ class DecoderBlockFn(torch.autograd.Function):
         with rt.probe("decoder.self_attn_bwd", replay=bwd_s):
             bwd_s()
         dw_jobs += [(dqk, xr, gsa_w[: 2 * d], gsa_b[: 2 * d]), (dv, xT, gsa_w[2 * d:], gsa_b[2 * d:])]
-        ops.linear_dx(dv, W["sa"][2 * d:], out=dx, accumulate=True)
+        ops.linear_dx(dv, W["sa"][2 * d:], out=dx, accumulate=True, wt=cols(WT["sa"], 2 * d, 3 * d))
         if not ops.linear_dx_rope(dqk, W["sa"][: 2 * d], dx, cos, sin, L):     # dx += rope_bwd(dqk W_qk)
             dxr = ops.linear_dx(dqk, W["sa"][: 2 * d])
             ops.rope_bwd(dxr, cos, sin, dx, L)

@@ -189,17 +189,61 @@ def linear(x2d, w, bias=None, out_dtype=None, out=None, epi=EPI_STORE, C2=None, 
                 drop_p=drop_p, seed=seed, rng_stream=rng_stream)
 
 
+# diagnostic A/B knob (tools/ab.sh): FDDM_DX_WT=0 runs every dX on W as stored and keeps no transposed copies (the
+# routing before they existed); a string of the letters s, a, d lets only the plain-store, the f32-accumulate and the
+# dGELU-fused dX use their copies (FDDM_DX_WT=sa is stage A of profiles/dx_gemm256.md); 1 = all three
+_DX_WT = os.environ.get("FDDM_DX_WT", "1")
+_DX_WT_CLASS = {EPI_STORE: "s", EPI_ACC: "a", EPI_DGELU: "d"}
+
+
+def dx_wt_enabled() -> bool:
+    return _DX_WT != "0"
+
+
 def linear_dx(dy2d, w, out=None, accumulate=False, out_dtype=torch.float32, epi=None, C2=None, drop_p=0.0, seed=0,
-              rng_stream=0):
-    """dx[M,K] = dy[M,N] @ w[N,K]  (w M/N-contiguous operand). accumulate -> out (f32) += ."""
+              rng_stream=0, wt=None):
+    """dx[M,K] = dy[M,N] @ w[N,K]  (w M/N-contiguous operand). accumulate -> out (f32) += .
+    wt (optional, bf16): w^T as a [K, N'] tensor whose rows hold w's columns (a column slice of a transposed weight
+    copy: stride(1) == 1, any row stride). The product then runs as an ordinary NT GEMM on the K-contiguous copy,
+    which lets fddm_gemm take the 256x256 kernel where its rule does (gemm_last_path tells); without wt, and with
+    FDDM_DX_WT=0, w is read as stored."""
     M, N = dy2d.shape
     K = w.shape[1]
     _chk(w.shape[0] == N and w.is_contiguous() and dy2d.stride(1) == 1, "linear_dx shapes")
     if out is None:
         out = torch.empty(M, K, device=dy2d.device, dtype=out_dtype)
     e = EPI_ACC if accumulate else (EPI_STORE if epi is None else epi)
+    if wt is not None and dy2d.dtype == torch.bfloat16 and (_DX_WT == "1" or _DX_WT_CLASS.get(e, "-") in _DX_WT):
+        _chk(tuple(wt.shape) == (K, N) and wt.stride(1) == 1 and wt.dtype == w.dtype, "linear_dx: wt is not w^T")
+        return gemm(dy2d, wt, out, M, K, N, a_kc=True, b_kc=True, lda=dy2d.stride(0), ldb=wt.stride(0),
+                    ldc=out.stride(0), epi=e, C2=C2, drop_p=drop_p, seed=seed, rng_stream=rng_stream)
     return gemm(dy2d, w, out, M, K, N, a_kc=True, b_kc=False, lda=dy2d.stride(0), ldb=K, ldc=out.stride(0), epi=e,
                 C2=C2, drop_p=drop_p, seed=seed, rng_stream=rng_stream)
+
+
+def transpose_table(pairs):
+    """Device table for transpose_bf16_mt over (src [rows, cols], dst [cols, rows]) pairs of contiguous bf16 tensors
+    (rows and cols multiples of 8): (table, tensors, workgroups). Built on the host; not inside a graph capture."""
+    rows_, nb = [], 0
+    for src, dst in pairs:
+        _chk(src.dim() == 2 and dst.dim() == 2 and src.dtype == torch.bfloat16 and dst.dtype == torch.bfloat16,
+             "transpose: 2-D bf16 tensors")
+        r, c = src.shape
+        _chk(tuple(dst.shape) == (c, r) and src.is_contiguous() and dst.is_contiguous(), "transpose: dst is not src^T")
+        _chk(r % 8 == 0 and c % 8 == 0 and r > 0 and c > 0, "transpose: rows and cols must be multiples of 8")
+        _chk(src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0 and src.data_ptr() != dst.data_ptr(),
+             "transpose: 16-B aligned, distinct buffers")
+        rows_ += [src.data_ptr(), dst.data_ptr(), r, c, nb]
+        nb += ((r + 63) // 64) * ((c + 63) // 64)
+    dev = pairs[0][0].device
+    tab = torch.tensor(rows_, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+    return tab, len(pairs), nb
+
+
+def transpose_bf16_mt(table):
+    """dst = src^T for every pair of a transpose_table(), one launch."""
+    tab, nt, nb = table
+    call("fddm_transpose_bf16_mt", tab.data_ptr(), nt, nb, stream())
 
 
 _NO_ROPE_FUSE = os.environ.get("FDDM_ROPE_FUSE", "1") == "0"     # diagnostic A/B knob (tools/ab.sh)

@@ -1,5 +1,7 @@
 """Fused clip_grad_norm_ + AdamW (train.py:411-423) over libfddm_hip: three launches per step, no
-host synchronisation, and the bf16 weight copies for the next forward written in the same pass.
+host synchronisation, and the bf16 weight copies for the next forward written in the same pass. Where the backward
+keeps transposed bf16 copies (runtime.wt_t, the decoder's input-gradient GEMMs), one more launch per parameter group
+rewrites them all from the plain copies (ops.transpose_bf16_mt).
 
 `state["step"]` is a 0-d fp32 tensor on the parameter's device (torch.optim.AdamW keeps a 0-d fp32 tensor
 too; its capturable/fused variants keep it on the device), advanced by the kernel, so a step skipped by the
@@ -10,6 +12,7 @@ import torch
 
 from . import runtime as rt
 from ._lib import call
+from . import ops
 from .ops import stream
 
 CHUNK = 65536
@@ -78,10 +81,13 @@ class FusedAdamW(torch.optim.Optimizer):
                 p.grad = None
 
     @staticmethod
-    def _bufs_live(plist, bufs) -> bool:
-        """The bf16 copies a table writes are still the runtime cache's live entries for their parameters."""
-        for p, b in zip(plist, bufs):
+    def _bufs_live(plist, bufs, tbufs) -> bool:
+        """The bf16 copies a table writes are still the runtime cache's live entries for their parameters, and so are
+        the transposed copies (runtime.wt_t): none replaced, dropped, or created since the table was built."""
+        for p, b, tb in zip(plist, bufs, tbufs):
             if b is not None and rt.bf16_entry(p) is not b:
+                return False
+            if b is not None and rt.wt_t_entry(p) is not tb:
                 return False
         return True
 
@@ -96,7 +102,7 @@ class FusedAdamW(torch.optim.Optimizer):
             # parameter changed in place): rebuild, so the kernel never writes a copy the forward no longer reads
             if t["gen"] == rt.wcache_generation():
                 return t
-            if self._bufs_live(plist, t["bufs"]):
+            if self._bufs_live(plist, t["bufs"], t["tbufs"]):
                 t["gen"] = rt.wcache_generation()
                 return t
             del self._tables[key]
@@ -107,7 +113,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("FusedAdamW: a chunk table would be built inside a HIP-graph capture (its host-to-"
                                "device copy cannot be captured); run one eager step of this parameter set first")
-        ct, cs, numel, pp, gp, mp, vp, bp, sp, bufs = [], [], [], [], [], [], [], [], [], []
+        ct, cs, numel, pp, gp, mp, vp, bp, sp, bufs, tbufs = [], [], [], [], [], [], [], [], [], [], []
         for i, p in enumerate(plist):
             st = self.state[p]
             n = p.numel()
@@ -124,12 +130,17 @@ class FusedAdamW(torch.optim.Optimizer):
                 b = rt.wt_bf16_buffer(p)
                 bufs.append(b)               # held by the table: the kernel never writes freed memory
                 bp.append(b.data_ptr())
+                tbufs.append(rt.wt_t_entry(p))   # the transposed copy, where the backward has asked for one
             else:
                 bufs.append(None)
+                tbufs.append(None)
                 bp.append(0)
         L = lambda v: torch.tensor(v, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)  # noqa: E731
         tab = dict(ct=L(ct), cs=L(cs), numel=L(numel), p=L(pp), g=L(gp), m=L(mp), v=L(vp), b=L(bp), s=L(sp),
-                   n=len(ct), nt=len(plist), bufs=bufs, gen=rt.wcache_generation())
+                   n=len(ct), nt=len(plist), bufs=bufs, tbufs=tbufs, gen=rt.wcache_generation())
+        # one transpose launch per step rewrites every transposed copy from the plain copy the AdamW kernel just wrote
+        pairs = [(b, tb) for b, tb in zip(bufs, tbufs) if tb is not None]
+        tab["tr"] = ops.transpose_table(pairs) if pairs else None
         self._tables[key] = tab
         return tab
 
@@ -194,6 +205,8 @@ class FusedAdamW(torch.optim.Optimizer):
                  float(group["lr"] * group["weight_decay"]), float(b1), float(b2), float(group["eps"]),
                  self._skipped.data_ptr() if gi == 0 else 0, int(bool(zero_grads)), float(grad_scale),
                  stream())   # skip counted once
+            if tab["tr"] is not None:
+                ops.transpose_bf16_mt(tab["tr"])
         if zero_grads and self.arena is not None:
             # every arena slot was in a table AND each .grad is still the arena view the kernel just zeroed (a grad
             # rebound above or by user code leaves its arena slot holding this step's values: zero_grad must fill)

@@ -142,6 +142,35 @@ def wt_bf16_buffer(p: torch.Tensor) -> torch.Tensor:
     return e.tensor
 
 
+_WT_T = "T"      # cache key of the transposed bf16 copy, next to (id(p), bfloat16, None)
+
+
+def _transposed_bf16(p: torch.Tensor) -> torch.Tensor:
+    src = wt(p, torch.bfloat16)
+    out = torch.empty(p.shape[1], p.shape[0], device=p.device, dtype=torch.bfloat16)
+    ops.transpose_bf16_mt(ops.transpose_table([(src, out)]))
+    return out
+
+
+def wt_t(p: torch.Tensor):
+    """W^T of a 2-D parameter as a contiguous bf16 [in, out] tensor: the K-contiguous operand of the input-gradient
+    GEMM dY W (ops.linear_dx wt=). Cached like the plain bf16 copy under (id(p), bfloat16, "T"): built on a miss
+    (ops.transpose_bf16_mt of the plain copy), rebuilt when p changed in place, dropped by clear_cache(), retained
+    under retaining(); FusedAdamW rewrites it in place right after every update of p. None where there is no such
+    copy: the fp32 precision mode, a parameter that is not 2-D, or a dimension that is not a multiple of 8."""
+    if _precision != "bf16" or p.dim() != 2 or p.shape[0] % 8 or p.shape[1] % 8 or not p.is_contiguous():
+        return None
+    if not ops.dx_wt_enabled():      # diagnostic switch FDDM_DX_WT=0: no copies, no transpose launch
+        return None
+    return wt(p, torch.bfloat16, transform=lambda _: _transposed_bf16(p), key=_WT_T)
+
+
+def wt_t_entry(p: torch.Tensor):
+    """The cached transposed bf16 copy currently served for p (None if there is none)."""
+    e = _wcache.get((id(p), torch.bfloat16, _WT_T))
+    return e.tensor if e is not None and e.ref() is p else None
+
+
 def clear_cache():
     global _wcache_gen, _cache_epoch
     _wcache.clear()

@@ -222,6 +222,11 @@ int fddm_embed_bwd(const long* tok, const float* dx, float* dE, float* dtb, long
 /* ---- helpers: column sums (bias grads), dtype casts */
 int fddm_colsum(int dtype, const void* X, float* out, long M, long N, long ldx, void* hip_stream);
 int fddm_cast(int src_dtype, int dst_dtype, const void* x, void* y, long n, void* hip_stream);
+/*      multi-tensor bf16 transpose in one launch: `table` (device) holds 5 longs per tensor — src [rows][cols], dst
+ *      [cols][rows] (both contiguous, 16-B aligned), rows, cols (multiples of 8), and the tensor's first workgroup
+ *      (the running sum of ceil(rows/64) * ceil(cols/64)); nblocks = that sum over all tensors. The caller vouches
+ *      for the table: the kernel checks nothing but each tensor's own extents. */
+int fddm_transpose_bf16_mt(const long* table, long ntensors, long nblocks, void* hip_stream);
 
 /* ---- discrete diffusion: q_sample draw (train.py:180-188; diffusion_scheduler.py:31-50) and the
  *      categorical KL + exact gradient (train.py:190-255). thr: [T] uint32 keep thresholds.
