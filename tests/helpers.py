@@ -855,14 +855,19 @@ class AttnBwdTerms:
     __slots__ = ("S", "P", "G", "delta", "T", "PD", "D", "c", "dq", "dk", "dv")
 
 
-def attn_fwd_ref64(q, k, v, keep, drop_keep, p, scale):
+def attn_fwd_ref64(q, k, v, keep, drop_keep, p, scale, bias=None):
     """Float64 forward: q [B, H, Lq, 64], k, v [B, H, Lk, 64] (any float dtype), keep [B, Lk] bool or None, drop_keep
-    [B, H, Lq, Lk] bool or None (oracle.attn_dropout_keep). Returns O [B, H, Lq, 64] and LSE [B, H, Lq] (natural log of
-    the scaled scores), both float64."""
+    [B, H, Lq, Lk] bool or None (oracle.attn_dropout_keep), bias [B, H, Lq, Lk] float64 or None (added to the scaled
+    scores: WavLM's gate times its relative-position table). Returns O [B, H, Lq, 64] and LSE [B, H, Lq] (natural log
+    of the scaled scores), both float64. A row without a kept key is NaN in both (softmax of all -inf), as in every
+    kernel."""
     s = float(scale) * (q.double() @ k.double().transpose(-1, -2))
+    if bias is not None:
+        s = s + bias
     if keep is not None:
         s = s.masked_fill(~keep[:, None, None, :], float("-inf"))
     lse = torch.logsumexp(s, -1)
+    lse = torch.where(torch.isinf(lse) & (lse < 0), torch.full_like(lse, float("nan")), lse)
     pr = torch.exp(s - lse[..., None])
     if drop_keep is not None:
         pr = pr * drop_keep.double() / (1.0 - float(p))
@@ -1508,3 +1513,555 @@ def gate_emulate(x, W, bias, cst, B, S, H):
     pb = ((r[..., 4] + r[..., 5]) + r[..., 6]) + r[..., 7]
     ga, gb = 1.0 / (1.0 + torch.exp(-pa)), 1.0 / (1.0 + torch.exp(-pb))
     return pa, pb, (ga * (gb * cst.float()[None, None, :] - 1.0) + 2.0).transpose(1, 2)
+
+
+# ------------------------------------------------- attention forward (csrc/attn7.hip, csrc/attn8.hip, csrc/attention.hip)
+# Reference, per-element units per kernel family, rounding-point emulation, inputs and the case table shared by
+# tests/test_cpu_attn_fwd_ref.py (which sets ATTN_FWD_E from the reference alone and proves with mutated references that
+# the bound tells real bugs apart) and tests/test_gpu_attn_fwd.py (which runs the kernels). DESIGN.md 4.10.
+class AttnFwdRef:
+    """Float64 pieces of one attention forward: S (scores with the bias, -inf at masked keys), P, D (c times the keep
+    bits, or None), c, O, LSE, m (row maximum of S), g / dg (the gate [B, H, L] and its own bound, or None), T (the
+    table gathered to [H, L, L], or None)."""
+    __slots__ = ("S", "P", "D", "c", "O", "LSE", "m", "g", "dg", "T")
+
+
+def attn_rel_index(L):
+    """[L, L]: the table column of (query i, key k), k - i + L - 1 (HF modeling_wavlm.py:474-513 through
+    models/wavlm.py's table layout; csrc/attn7.hip :176)."""
+    return torch.arange(L)[None, :] - torch.arange(L)[:, None] + L - 1
+
+
+def attn_fwd_gate64(src, B, H, L, *, gate=None, graw=None, x=None, gw=None, gconst=None):
+    """The query gate of WavLM's biased attention in float64 on the kernel's own inputs, and the bound dg of the
+    kernel's gate against it (gate_bound: the form and the constant pinned for fddm_wavlm_gate; the in-kernel forms
+    compute the same expression with the same __expf). Both [B, H, L].
+      "gate": the precomputed fp32 row [B H, L] as given, dg = 0;
+      "graw": the 4 + 4 bf16 pre-activations [B L, >= 8 H] summed, two sigmoids, ga (gb gconst[h] - 1) + 2
+              (attn7.hip :280-288, attention.hip :582-590);
+      "gx":   x [B L, >= 64 H] (bf16) against models.wavlm._fold_gate's 130 floats (attn7.hip :289-311,
+              attention.hip :593-620)."""
+    if src == "gate":
+        g = gate.double().reshape(B, H, L)
+        return g, torch.zeros_like(g)
+    if src == "graw":
+        p = graw.double()[:, :H * 8].reshape(B, L, H, 8)
+        sp = p.abs()
+    else:
+        xh, w = x.double()[:, :H * 64].reshape(B, L, H, 64), gw.double()
+        p = torch.zeros(B, L, H, 8, dtype=torch.float64)
+        sp = torch.zeros_like(p)
+        for j, (lo, bi) in enumerate(((0, 128), (64, 129))):
+            p[..., 4 * j] = xh @ w[lo:lo + 64] + w[bi]
+            sp[..., 4 * j] = xh.abs() @ w[lo:lo + 64].abs() + w[bi].abs()
+    r = gate_out64(p, sp, gconst)
+    return r.ref, gate_bound(r)
+
+
+def attn_fwd_terms64(q, k, v, keep, drop_keep, p, scale, gate=None, dg=None, table=None):
+    """The operation every forward entry point defines, in float64 on the values the C ABI receives (bf16 or f32 Q, K, V
+    as [B, H, L, 64]; keep [B, Lk] bool or None with the keys at and past key_len[b] already false; the oracle's keep
+    bits; p = attn_p32(p); the fp32 table [H, 2 L - 1] with the float64 gate of attn_fwd_gate64):
+        S_ik = s Q_i.K_k + g_i T[h][k - i + Lk - 1]      P = softmax over kept keys      LSE_i = logsumexp_k S_ik
+        O_id = c sum_k P_ik D_ik V_kd,  c = 1 / (1 - p)
+    O and LSE come from attn_fwd_ref64. A row without a kept key is NaN in O and LSE. Returns an AttnFwdRef."""
+    r = AttnFwdRef()
+    r.g, r.dg = gate, dg
+    r.T = table.double()[:, attn_rel_index(k.shape[2])] if table is not None else None
+    bias = gate[..., None] * r.T[None] if table is not None else None
+    r.O, r.LSE = attn_fwd_ref64(q, k, v, keep, drop_keep, p, scale, bias)
+    s = float(scale) * (q.double() @ k.double().transpose(-1, -2))
+    if bias is not None:
+        s = s + bias
+    if keep is not None:
+        s = s.masked_fill(~keep[:, None, None, :], float("-inf"))
+    r.S, r.m = s, s.max(-1).values
+    r.P = torch.exp(s - r.LSE[..., None])
+    r.c = 1.0 / (1.0 - float(p)) if drop_keep is not None else 1.0
+    r.D = drop_keep.double() * r.c if drop_keep is not None else None
+    return r
+
+
+ATTN_FWD_FAMILY = {"fwd7": "7", "fwd8": "8", "fwd6": "16", "fwd2": "16", "fwd5": "16", "generic": "f32"}
+
+
+def attn_fwd_units(family, r, q, k, v, scale, tripped=None):
+    """Per-element units of an AttnFwdRef for the checks
+        |O_gpu - O_ref|     <= C_O u b_O + rel |O_ref| + lin_O
+        |LSE_gpu - LSE_ref| <= C_L u b_LSE + lin_LSE
+    as a dict (u, rel, b_o, b_lse, lin_o, lin_lse). u = 2^-9 and rel = 2^-8 (O is stored as bf16) for the bf16
+    families, u = 2^-24 and rel = 0 for "f32". With a_ik = s sqrt(sum_d Q_id^2 K_kd^2), e_ikd = c D_ik V_kd and every
+    sum over the kept keys k, the rounding points, each a relative error of at most u on the value it rounds, and the
+    root-sum-square size they give an output:
+
+    family "7" (fwd7_kernel, every build, attn7.hip :214-525; also the rows fwd8's fallback recomputes, attn8.hip
+    :608-663, which is fwd7's algorithm with f32 row sums, :303-314):
+      (1) Q' = bf16(Q s log2 e) (scale_frag, :269): one rounding eps_id' per query element, shared by every key of the
+          row. It moves S_ik by s sum_d' eps_id' Q_id' K_kd', hence LSE_i by s sum_d' eps_id' Q_id' Kbar_id' with
+          Kbar_i = sum_k P_ik K_k, and O_id by s sum_d' eps_id' Q_id' M_id'd with M_i = sum_k P_ik K_k (e_ik - O_i)^T
+          (64 x 64 per row). Taking the keys' errors as independent (u a_ik per score) underrates both by the factor
+          by which P and K are correlated along Q, about 4 at Lk 1024 on random inputs: the first emulation run showed
+          it, the LSE of fwd7 at (96, 1024) sat at 10.5 of those units;
+      (2) P o D packed to bf16 for the PV MFMA (:438); the row sum takes the fp32, undropped P (:432-433, :470): a
+          relative u on every term P_ik e_ikd of O, nothing on LSE;
+      (3) O rounded to bf16 (:511): the rel term.
+      The softmax reference rf is bf16-exact inside the score MFMA (:376, :460, :468), the mask is an exact 0 / -inf
+      (:338), the bias FMA (:415), exp2 (:430) and __log2f (:517) are fp32.
+          b_O^2 = s^2 sum_d' Q_id'^2 M_id'd^2 + sum_k P_ik^2 e_ikd^2     b_LSE^2 = s^2 sum_d' Q_id'^2 Kbar_id'^2
+    family "8" (fwd8_kernel's fast path, attn8.hip): (1) (:225-226) and (3) (:687-688) as above; the row sums come from
+      row-selector MFMAs on the packed, undropped bf16 P (:6-9, :33-37, :589, :597) and the PV operand is that same
+      packed value under the keep mask (:373-389), so one rounding of P_ik enters the numerator and the denominator
+      together and moves O by P_ik (e_ikd - O_id), not by P_ik e_ikd, and LSE by P_ik:
+          b_O^2 = s^2 sum_d' Q_id'^2 M_id'd^2 + sum_k P_ik^2 (e_ikd - O_id)^2
+          b_LSE^2 = s^2 sum_d' Q_id'^2 Kbar_id'^2 + sum_k P_ik^2
+      `tripped` [B, H, Lq] marks the rows whose wave took the fallback (attn_fwd_emulate returns it): family "7" units.
+      tripped = "either" (the fwd8 guard cases) takes the larger of the two units per element instead: there the rows
+      that fall back are the kernel's to decide, and tests/test_gpu_attn7.py's guard test pins which ones must.
+    family "16" (fwd6 / fwd2 / fwd5, attention.hip): Q is not pre-scaled, scores, bias and mask are fp32 (fwd2
+      :418-425, :455; fwd5 :710-715, :747; fwd6 likewise), so (1) does not exist; P o D is packed to bf16 (fwd2
+      :488-491, fwd5 :780-783, fwd6 :1107-1110), the row sum is fp32 (:457, :477), O is bf16 (:529, :829, :1167), the
+      LSE is fp32 (:534, :834, :1172):
+          b_O^2 = sum_k P_ik^2 e_ikd^2                                      b_LSE = the fp32 terms below
+    family "f32" (fwd_kernel<float>, attention.hip :190-269): nothing rounds to bf16. u = 2^-24; the fast __expf of
+      every probability (:245) is taken as gate_out64 takes it, (|S_ik - m_i| + 4) u relative on P_ik, in numerator and
+      denominator alike; __logf (:268) is in the floor.
+    fp32 terms, every family (sqrt(n) 2^-24 of the root-sum-square of the n products, as attn_bwd_units (7)): the
+      64-term score sums move S_ik by 8 a_ik 2^-24; the bias FMA by 2 |g_i T_ik| 2^-24 (the product and the sum); the
+      Lk-term PV and row sums give sqrt(Lk) 2^-24 sqrt(sum_k P_ik^2 (e_ikd^2 + O_id^2)) on O and sqrt(Lk) 2^-24
+      sqrt(sum_k P_ik^2) on LSE. All enter b in quadrature (they are 2^-15 of a unit for the bf16 families).
+    lin_LSE starts from the floor, written out: 2^-24 (8 + 4 |m_i| + 4 |LSE_i| + nt (R_i + 4)), m_i the row's largest
+      score, R_i = m_i - its smallest kept score, nt = ceil(Lk / 64): the exponent's argument is an fp32 difference of
+      two terms of size up to |m| log2 e (4 |m|), the LSE is an fp32 sum and product of terms of size |LSE| log2 e
+      (4 |LSE|), exp2 / log2 / __logf are good to an ulp (8), and each of the nt rescalings of the online softmax
+      multiplies the sum by an exponential of an argument of at most R_i (the f32 family's __expf: (R_i + 4) each).
+    Gate term (a table was given): the kernel's gate differs from float64 by at most dg_i (attn_fwd_gate64) plus
+      2 2^-24 |g_i| for its fp32 rescaling (g log2 e, attn7.hip :313; g / s, attention.hip :356 / :657). It moves every
+      score of row i together, so it is added linearly:
+          lin_O += dg_i |sum_k P_ik T_ik (e_ikd - O_id)|                   lin_LSE += dg_i |sum_k P_ik T_ik|"""
+    f32 = family == "f32"
+    u = U24 if f32 else U9
+    s, Lk = float(scale), k.shape[2]
+    v2 = v.double()
+    a2 = s * s * ((q.double() ** 2) @ (k.double() ** 2).transpose(-1, -2))
+    W = r.P ** 2
+    Dc = r.D if r.D is not None else 1.0
+
+    def sums(Wt):       # sum_k Wt (e - O)^2 and sum_k Wt e^2, [B, H, Lq, 64]
+        WD = Wt * Dc
+        A2 = (WD * Dc) @ v2 ** 2
+        return (A2 - 2.0 * r.O * (WD @ v2) + r.O ** 2 * Wt.sum(-1, keepdim=True)).clamp_min(0.0), A2
+
+    gT = r.g[..., None] * r.T[None] if r.T is not None else None
+    fs2 = 64.0 * a2 + (4.0 * gT ** 2 if gT is not None else 0.0)
+    if f32:
+        arg = (r.S - r.m[..., None]).abs()
+        fs2 = fs2 + (torch.where(torch.isfinite(arg), arg, torch.zeros_like(arg)) + 4.0) ** 2
+    sig2 = U24 ** 2 * fs2
+    devW, A2W = sums(W)
+    dev_s, _ = sums(W * sig2)
+    Wsum = W.sum(-1)
+    fo2 = U24 ** 2 * Lk * (A2W + r.O ** 2 * Wsum[..., None])
+    var_o = dev_s + (0.0 if f32 else u * u * A2W) + fo2
+    var_l = (W * sig2).sum(-1) + U24 ** 2 * Lk * Wsum
+    vq_o = 0.0
+    if family in ("7", "8"):        # point (1), per (b, h) and in chunks of rows: M is [rows, 64, 64]
+        kd, q2 = k.double(), q.double() ** 2
+        Kbar = r.P @ kd
+        var_l = var_l + u * u * s * s * (q2 * Kbar ** 2).sum(-1)
+        PD = r.P * Dc
+        vq = torch.empty_like(r.O)
+        step = max(1, (1 << 22) // (Lk * 64))
+        for b in range(q.shape[0]):
+            for h in range(q.shape[1]):
+                for i0 in range(0, q.shape[2], step):
+                    i = slice(i0, i0 + step)
+                    M = (PD[b, h, i, :, None] * kd[b, h][None]).transpose(1, 2) @ v2[b, h]
+                    M = M - Kbar[b, h, i, :, None] * r.O[b, h, i, None, :]
+                    vq[b, h, i] = torch.einsum("rd,rde->re", q2[b, h, i], M ** 2)
+        vq_o = u * u * s * s * vq
+        var_o = var_o + vq_o
+    if family == "8":
+        var_o8, var_l8 = dev_s + vq_o + u * u * devW + fo2, var_l + u * u * Wsum
+        if isinstance(tripped, str):     # the guard cases: which waves fell back is the kernel's business, so the larger unit
+            var_o, var_l = torch.maximum(var_o, var_o8), var_l8
+        else:
+            t = tripped if tripped is not None else torch.zeros_like(Wsum, dtype=torch.bool)
+            var_o, var_l = torch.where(t[..., None], var_o, var_o8), torch.where(t, var_l, var_l8)
+    smin = torch.where(torch.isinf(r.S), torch.full_like(r.S, float("inf")), r.S).min(-1).values
+    lin_l = U24 * (8.0 + 4.0 * r.m.abs() + 4.0 * r.LSE.abs() + ((Lk + 63) // 64) * (r.m - smin + 4.0))
+    lin_o = torch.zeros_like(r.O)
+    if gT is not None:
+        dgt = r.dg + 2.0 * U24 * r.g.abs()
+        PT = r.P * r.T[None]
+        lin_l = lin_l + dgt * PT.sum(-1).abs()
+        lin_o = dgt[..., None] * ((PT * Dc) @ v2 - r.O * PT.sum(-1, keepdim=True)).abs()
+    return dict(u=u, rel=0.0 if f32 else 2.0 ** -8, b_o=var_o.sqrt() / u, b_lse=var_l.sqrt() / u, lin_o=lin_o,
+                lin_lse=lin_l)
+
+
+def attn_fwd_excess(got, ref, b, u, rel=0.0, lin=0.0):
+    """(|got - ref| - rel |ref| - lin)+ in units of u b, per element, in the shape of attn_bwd_excess: 0 where b == 0
+    and nothing is left, inf where b == 0 and something is. Where the reference is NaN (a row without a kept key) the
+    kernel's value must be NaN too: 0 if it is, inf if not, and inf where got is NaN and the reference is not."""
+    got = got.double()
+    x = ((got - ref).abs() - rel * ref.abs() - lin).clamp_min(0.0)
+    out = x / (u * b)
+    inf = torch.full_like(x, float("inf"))
+    out = torch.where(b == 0, torch.where(x == 0, torch.zeros_like(x), inf), out)
+    rn, gn = torch.isnan(ref), torch.isnan(got)
+    return torch.where(rn | gn, torch.where(rn & gn, torch.zeros_like(x), inf), out)
+
+
+def attn_fwd_emulate(family, q, k, v, keep, drop_keep, p, scale, gate=None, table=None):
+    """The kernels' rounding points in plain torch: fp32 where the kernel holds fp32, .to(bfloat16) at the points of
+    attn_fwd_units. Not modelled: the MFMA summation order, the hardware exp2, FMA contraction, the tile-by-tile
+    rescaling of the online softmax (the reference is the row's final one; fwd8's is that of its first 32 keys, as in
+    the kernel), the gate's own arithmetic (the float64 gate rounded to fp32 goes in). It sets ATTN_FWD_E and proves
+    statements about inputs; it is no oracle for the kernels. Returns (O float32 [B, H, Lq, 64], holding bf16 values
+    for the bf16 families; LSE float32 [B, H, Lq]; tripped [B, H, Lq] bool for family "8", else None)."""
+    f = torch.float32
+    q, k, v = (x.to(f) for x in (q, k, v))
+    sc = float(np.float32(scale))
+    sl2 = float(np.float32(sc * LOG2E_F32))
+    Lq, Lk = q.shape[2], k.shape[2]
+    Tm = table.to(f)[:, attn_rel_index(Lk)][None] if table is not None else None
+    g = gate.to(f) if gate is not None else None
+    D = drop_keep.to(f) if drop_keep is not None else None
+    c = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p))) if D is not None else 1.0
+    kT = k.transpose(-1, -2)
+    nan = torch.tensor(float("nan"))
+
+    def mask(s):
+        return s if keep is None else s.masked_fill(~keep[:, None, None, :], float("-inf"))
+
+    def ref_of(mx, rnd):
+        return torch.where(torch.isinf(mx), torch.zeros_like(mx), rnd(mx))
+
+    tripped = None
+    if family in ("7", "8"):
+        s2 = _bf(q * sl2) @ kT
+        if Tm is not None:
+            s2 = s2 + (g * LOG2E_F32)[..., None] * Tm
+        s2 = mask(s2)
+        rf = ref_of(s2.max(-1).values, _bf)
+        P = torch.exp2(s2 - rf[..., None])
+        l = P.sum(-1)
+        PD = _bf(P if D is None else P * D)
+        if family == "8":
+            rf8 = ref_of(s2[..., :32].max(-1).values, _bf)
+            P8 = _bf(torch.exp2(s2 - rf8[..., None]))
+            l8 = P8.sum(-1)
+            trip = ~((l8 >= 2.0 ** -40) & (l8 <= 2.0 ** 64)) & (l > 0)
+            pad = (-Lq) % 64        # the guard is per wave: 64 consecutive queries fall back together
+            tw = torch.nn.functional.pad(trip, (0, pad)).unflatten(-1, (-1, 64)).any(-1, keepdim=True)
+            tripped = tw.expand(*tw.shape[:-1], 64).flatten(-2)[..., :Lq]
+            PD = torch.where(tripped[..., None], PD, P8 if D is None else P8 * D)
+            l, rf = torch.where(tripped, l, l8), torch.where(tripped, rf, rf8)
+        o = _bf((PD @ v) * (c / l)[..., None])
+        lse = (rf + torch.log2(l)) * LN2_F32
+    elif family == "16":
+        x = q @ kT
+        if Tm is not None:
+            x = x + (g / sc)[..., None] * Tm
+        x = mask(x)
+        m = ref_of(x.max(-1).values, lambda t: t)
+        P = torch.exp2(x * sl2 - (m * sl2)[..., None])
+        l = P.sum(-1)
+        o = _bf((_bf(P if D is None else P * D) @ v) * (c / l)[..., None])
+        lse = (m * sl2 + torch.log2(l)) * LN2_F32
+    else:
+        nthr = torch.get_num_threads()      # here the fp32 sums are the whole error: one thread, so that the summation
+        torch.set_num_threads(1)            # order, and with it the measured E, does not depend on the thread count
+        try:
+            x = (q @ kT) * sc
+            if Tm is not None:
+                x = x + g[..., None] * Tm
+            x = mask(x)
+            m = ref_of(x.max(-1).values, lambda t: t)
+            P = torch.exp(x - m[..., None])
+            l = P.sum(-1)
+            o = ((P if D is None else P * D * c) @ v) / l[..., None]
+        finally:
+            torch.set_num_threads(nthr)
+        lse = m + torch.log(l)
+    dead = ~(l > 0)
+    return torch.where(dead[..., None], nan, o), torch.where(dead, nan, lse), tripped
+
+
+# The largest error of attn_fwd_emulate against the float64 reference in units of u b (after the rel and lin terms),
+# over every case of attn_fwd_cases() and every input set, per kernel family and output, measured on the CPU
+# (tests/test_cpu_attn_fwd_ref.py asserts stored <= 1.1 measured + ATTN_FWD_E_FLOOR and measured <= stored). The kernels
+# are allowed ATTN_FWD_C = 2 E units, the backward's factor and reason: what the emulation leaves out is fp32-sized and
+# inside the units, so the factor covers only the tail between one sample of roundings and another.
+# Measured (O / LSE): family 7 3.88 / 3.47, family 8 4.07 / 3.22, family 16 3.44 / 0 and f32 2.61 / 0: the LSE of the
+# families that keep it in fp32 never leaves the written-out floor, their E is the floor of the rule.
+ATTN_FWD_E = {"7": dict(o=4.1, lse=3.65), "8": dict(o=4.3, lse=3.4), "16": dict(o=3.6, lse=0.05),
+              "f32": dict(o=2.75, lse=0.05)}
+ATTN_FWD_E_FLOOR = 0.05
+ATTN_FWD_C = {f: {n: 2.0 * e for n, e in d.items()} for f, d in ATTN_FWD_E.items()}
+
+ATTN_REL_SPIKES = (129, 128, 127, 65, 64, 63, 33, 32, 31, 1)     # and their negatives, 0 and +-(S - 1)
+ATTN_FWD_SHAPES = ((1, 1), (33, 5), (65, 17), (64, 64), (129, 200), (256, 256), (40, 257), (129, 300), (257, 64),
+                   (40, 513), (96, 1024))
+ATTN_FWD_FAINT = 2.0 ** -6      # the "faint" input set: the flat q times this
+ATTN_REL_SPIKE_MASS = 2.0 / 3.0  # of the median row before the last key's weight: half of the row after it
+ATTN_REL_LAST_MASS = 0.25       # the last kept key's share of every row, WavLM "edges"
+ATTN_REL_QW_MIN, ATTN_REL_QW_MAX = 4.0, 32.0    # the range of a query's component along w
+
+
+def _fc(kernel, Lq, Lk, masked=False, p=0.0, *, force, ext=None, bits=None, strided=False, guard=False, B=2, H=2,
+        src=None, g8=None, faint=False, dead=False, tag=""):
+    """One forward case. kernel: what ops.attn_last_path()["fwd"][0] must read; expect: the whole tuple (kernel, DM, MK,
+    KX, REL). bits: None (no dropout), "ready" (the producer wrote the keep bits, the forward reads them), "own" (the
+    forward gets an unwritten buffer and it, or the launch wrapper for it, writes the words), "rehash" (no buffer).
+    src: the gate source of a WavLM case ("gate" | "graw" | "gx"), None for the decoder's. g8: (geometry, kind, c) of
+    fwd8_guard_inputs. dead: the last entry's mask keeps no key. The f32 family runs fp32 tensors."""
+    rel, kx = src is not None, ext is not None
+    if kx:
+        B, masked = len(ext), True
+    mk = 2 if masked else 1 if Lk % 64 else 0
+    m01 = int(masked or Lk % 64 != 0)
+    expect = {"fwd7": ("fwd7", int(p > 0), mk, kx, rel),
+              "fwd8": ("fwd8", int(p > 0), mk, False, False),
+              "fwd6": ("fwd6", 0 if p == 0 else 1 if bits == "ready" else 2, mk, False, False),
+              "fwd2": ("fwd2", int(p > 0), m01, False, False),
+              "fwd5": ("fwd5", 0, m01, False, True),
+              "generic": ("generic", int(p > 0), int(masked), False, False)}[kernel]
+    cid = (f"{kernel}-{Lq}x{Lk}" + ("-" + "_".join(map(str, ext)) if kx else "") + ("-mask" if masked and not kx else "")
+           + (f"-p{p}-{bits}" if p else "") + (f"-{src}" if rel else "") + ("-strided" if strided else "")
+           + ("-guard" if guard else "") + (f"-{force}" if force not in ("fwd7", "fwd8", "v6") else "")
+           + ("-dead" if dead else "") + tag)
+    kinds = ("guard",) if g8 else ("flat", "edges", "faint") if faint else ("flat", "edges")
+    return dict(id=cid, kernel=kernel, family=ATTN_FWD_FAMILY[kernel], B=B, H=H, Lq=Lq, Lk=Lk, masked=masked, p=p,
+                ext=ext, force=force, bits=bits, strided=strided, guard=guard, src=src, rel=rel, g8=g8, kinds=kinds, dead=dead,
+                f32=kernel == "generic", expect=expect, has_lse=src in (None, "gate"))
+
+
+@functools.lru_cache(maxsize=None)
+def attn_fwd_cases():
+    """Every case of tests/test_gpu_attn_fwd.py: the smallest shapes at which each mechanism of each forward kernel
+    exists (B H <= 8). guard: O is a column slice of a wider NaN-filled buffer; strided: q, k, v are column slices of
+    one [rows, 3 H 64] buffer."""
+    cs = []
+    # the decoder's kernels (no table): one query and key | a partial 32-query group, five keys | two query groups, 17
+    # keys | exactly one tile | ragged fourth key tile | four full tiles | one key in the fifth tile | ragged fifth |
+    # three query blocks of fwd7, two of fwd8 | one key in the ninth tile | sixteen full tiles
+    for kernel, force in (("fwd7", "fwd7"), ("fwd8", "fwd8"), ("fwd6", "v6")):
+        for si, (Lq, Lk) in enumerate(ATTN_FWD_SHAPES):
+            for masked in (False, True):
+                for p in (0.0, 0.1):
+                    # both ways of getting the keep bits under every mask build: alternate over shapes and masks
+                    bits = None if p == 0 else ("ready", "own")[(si + masked) % 2]
+                    cs.append(_fc(kernel, Lq, Lk, masked, p, force=force, bits=bits, guard=p > 0 and masked,
+                                  faint=kernel == "fwd7" and (Lq, Lk) in ((129, 200), (96, 1024))))
+        # more than eight query blocks of 128 (fwd7 / fwd6), five of 256 (fwd8), the last with one query
+        cs.append(_fc(kernel, 1025, 64, False, 0.0, force=force, B=1))
+        cs.append(_fc(kernel, 1025, 64, True, 0.1, force=force, B=1, bits="ready", guard=True))
+        # q | k | v from one fused-projection buffer
+        cs.append(_fc(kernel, 129, 200, True, 0.1, force=force, bits="ready", strided=True))
+    # the default dispatch at these small grids is fwd7 (attention.hip run<>: load8 > load7)
+    cs.append(_fc("fwd7", 129, 200, True, 0.1, force="auto", bits="ready"))
+    cs.append(_fc("fwd7", 65, 17, False, 0.0, force="auto"))
+    # key extents (fddm_attn_fwd_kx): always fwd7's KX builds
+    for Lk, ext in ATTN_KX.items():
+        for p in (0.0, 0.1):
+            cs.append(_fc("fwd7", 129, Lk, True, p, force="fwd7", ext=ext, H=1 if Lk == 200 else 2,
+                          bits="ready" if p else None, guard=p > 0))
+    # ... and an entry without a key: NaN rows in O and LSE
+    cs.append(_fc("fwd7", 129, 200, True, 0.0, force="fwd7", ext=[200, 0]))
+    # fwd8 alone: three workgroups, the last partial | exactly one half-tile | one key in the second half
+    cs.append(_fc("fwd8", 600, 300, True, 0.1, force="fwd8", bits="ready"))
+    cs.append(_fc("fwd8", 32, 32, False, 0.1, force="fwd8", B=1, H=1, bits="own"))
+    cs.append(_fc("fwd8", 64, 33, False, 0.0, force="fwd8", B=1))
+    # ... and two of its guard cases, whose designated rows' waves take the fallback
+    for geom, kind, cc in (("a", "rise", 4.7), ("b", "fall", 25.0)):
+        B, H, Lq, Lk, p, tail, _ = FWD8_GUARD_GEOMS[geom]
+        cs.append(_fc("fwd8", Lq, Lk, bool(tail) or kind == "fall", p, force="fwd8", B=B, H=H, bits="ready",
+                      g8=(geom, kind, cc), tag=f"-{kind}{cc}"))
+    # Lk > 1024: fwd2 whatever is forced; it draws its own keep bits and records them when it has a buffer
+    for Lq, Lk in ((40, 1025), (130, 1100)):
+        for masked in (False, True):
+            for p, bits in ((0.0, None), (0.1, "own"), (0.1, "rehash")):
+                cs.append(_fc("fwd2", Lq, Lk, masked, p, force="fwd7", bits=bits, guard=masked and bits == "own",
+                              tag="-long"))
+    # ... and its unmasked builds: Lk a multiple of 64
+    cs.append(_fc("fwd2", 40, 1088, False, 0.0, force="fwd7", B=1, tag="-long"))
+    cs.append(_fc("fwd2", 40, 1088, False, 0.1, force="fwd7", B=1, bits="own", tag="-long"))
+    # the generic f32 kernel
+    cs.append(_fc("generic", 65, 17, False, 0.0, force="auto"))
+    cs.append(_fc("generic", 129, 200, True, 0.1, force="auto", bits="rehash", guard=True))
+    cs.append(_fc("generic", 40, 257, False, 0.1, force="auto", bits="rehash"))
+    # WavLM's gated relative-position bias (a table; Lq = Lk = S, no dropout, H = 3 so that h (2 S - 1) is no multiple
+    # of anything convenient): fwd7's REL builds, and fwd5 forced (S > 1024 takes fwd5 whatever is forced)
+    for kernel, force, more in (("fwd7", "auto", ()), ("fwd5", "relfwd5", (1030, 1100))):
+        for S in (1, 33, 64, 127, 128, 129, 200, 257, 513, 1024) + more:
+            for src in ("gx", "gate", "graw") if S in (129, 257) else ("gx",):
+                cs.append(_fc(kernel, S, S, force=force, src=src, B=2 if S <= 257 else 1, H=3,
+                              faint=kernel == "fwd7" and S == 200))
+        # a key-padding mask without an extent (attn_fwd with gate + table + key_keep)
+        cs.append(_fc(kernel, 200, 200, True, force=force, src="gate", H=3))
+        # ... and with one (attn_fwd_relgate_x with key_keep and key_len): the ATTN_KX extents two entries at a time,
+        # and an entry without a key
+        for S, exts in ((200, ([200, 1], [63, 64], [65, 129])), (300, ([300, 257], [256, 70])), (129, ([129, 0],))):
+            for ext in exts:
+                cs.append(_fc(kernel, S, S, force=force, src="gx", ext=ext, H=3))
+    cs.append(_fc("generic", 129, 129, True, force="auto", src="gate", H=3))
+    # an entry whose mask keeps no key (no extent): NaN rows in O and LSE from every kernel
+    for kernel, force in (("fwd7", "fwd7"), ("fwd8", "fwd8"), ("fwd6", "v6"), ("generic", "auto")):
+        cs.append(_fc(kernel, 65, 17, True, 0.0, force=force, dead=True))
+    cs.append(_fc("fwd2", 40, 1025, True, 0.0, force="fwd7", dead=True, tag="-long"))
+    for kernel, force in (("fwd7", "auto"), ("fwd5", "relfwd5")):
+        cs.append(_fc(kernel, 129, 129, True, force=force, src="gate", H=3, dead=True))
+    assert len({c["id"] for c in cs}) == len(cs)
+    return cs
+
+
+# the template builds the case table must reach, as ops.attn_last_path()["fwd"] reads them (attention.hip run<>,
+# attn7.hip attn7_fwd, attn8.hip attn8_fwd). fwd2_kernel<.., REL = true> is instantiated nowhere: run<> launches fwd2
+# with REL = false only (attention.hip :2497), a table with Lk > 1024 takes fwd5.
+ATTN_FWD_BUILDS = (
+    [("fwd7", dm, mk, False, False) for dm in (0, 1) for mk in (0, 1, 2)] +
+    [("fwd7", dm, 2, True, False) for dm in (0, 1)] +
+    [("fwd7", 0, mk, False, True) for mk in (0, 1, 2)] + [("fwd7", 0, 2, True, True)] +
+    [("fwd8", dm, mk, False, False) for dm in (0, 1) for mk in (0, 1, 2)] +
+    [("fwd6", dm, mk, False, False) for dm in (0, 1, 2) for mk in (0, 1, 2)] +
+    [("fwd2", dm, mask, False, False) for dm in (0, 1) for mask in (0, 1)] +
+    [("fwd5", 0, mask, False, True) for mask in (0, 1)] +
+    [("generic", dm, mask, False, False) for dm, mask in ((0, 0), (1, 1), (1, 0), (0, 1))])
+
+
+def _bisect(f, hi, target=0.5, steps=14):
+    """The x in [0, hi] at which the increasing f reaches target (hi if it never does)."""
+    lo = 0.0
+    for _ in range(steps):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if f(mid) < target else (lo, mid)
+    return 0.5 * (lo + hi)
+
+
+def _median_mass(s, sel):
+    """Median over the rows with a kept key of the probability mass softmax(s) puts on the keys `sel` selects."""
+    pr = torch.softmax(s, -1)
+    m = (pr * sel).sum(-1)
+    return m[torch.isfinite(m)].median().item()
+
+
+@functools.lru_cache(maxsize=6)
+def attn_fwd_case_inputs(cid, kind):
+    """Inputs of case `cid` for input set `kind`, built once and never modified: a dict of q [B, Lq, H 64], k, v
+    [B, Lk, H 64] float32 (holding bf16 values unless the case runs the f32 kernel); keep [B, Lk] bool or None (keys at
+    and past an extent are false); drop [B, H, Lq, Lk] bool or None; for a WavLM case also table [H, 2 S - 1], gconst
+    [H], gw [130] float32, x [B S, H 64] and graw [B S, 8 H] float32 holding bf16 values, gate [B H, S] float32, and
+    g64 / dg [B, H, S] (attn_fwd_gate64 of the case's source).
+    "flat": randn q, k, v; table = 2 randn. "faint": the flat q times 2^-6 (a_ik of attn_fwd_units shrinks to
+      2^-6 of its flat size while P stays a bf16-sized rounding away from its row sum: the input set on which a P
+      rounded before the row sum shows in the LSE).
+    "edges", decoder: attn_bwd_case_inputs' recipe (q = 0.5 randn + 4 w, every edge key + beta w with beta from
+      ATTN_EDGE_MASS, masked keys the same + beta w).
+    "edges", WavLM: q = 0.5 randn (so that a single spike is not drowned); table = 2 randn plus a spike h at each
+      offset k - i in +-ATTN_REL_SPIKES, 0 and +-(S - 1) that exists, h solved (bisection on the reference's softmax) so
+      that at the case's gates the spiked keys hold ATTN_REL_SPIKE_MASS = 2/3 of the median row, which is half of it
+      once the last key has its quarter. As i runs over a query block every spike lands on every lane position, tile
+      edge and shifted-copy parity. The mask and tile-edge mutants need a key every row sees, and a table entry is seen
+      by one row per key while the 2 randn table moves a key's share by e^(+-g 2) from row to row: so the last kept key
+      of every entry gets + 8 w and query i gets + alpha_i w (w: 64 entries of +-1/8), alpha_i in [4, 32] solved per row
+      so that this key holds ATTN_REL_LAST_MASS = 1/4 of row i (more where 4 w already gives it more); the w component
+      adds N(0, (alpha_i / 8)^2) to every other score of the row. Masked keys get + 16 w: a kernel that keeps one shows
+      it in every row.
+    "guard": fwd8_guard_inputs of the case's g8."""
+    import math
+    from oracle import fddm_oracle as O
+    c = {x["id"]: x for x in attn_fwd_cases()}[cid]
+    B, H, Lq, Lk, p = c["B"], c["H"], c["Lq"], c["Lk"], c["p"]
+    drop = O.attn_dropout_keep(ATTN_SEED, ATTN_STREAM, B, H, Lq, Lk, p) if p > 0 else None
+    rnd = (lambda t: t.float()) if c["f32"] else (lambda t: t.to(torch.bfloat16).float())
+    if c["g8"]:
+        q, k, v, keep, _ = fwd8_guard_inputs(*c["g8"])
+        return dict(q=rnd(q), k=rnd(k), v=rnd(v), keep=keep, drop=drop)
+    gen = torch.Generator().manual_seed(104729 * Lq + 31 * Lk + 7 * c["masked"] + (1 if kind == "edges" else 0))
+    q, k, v = (torch.randn(B, L, H, 64, generator=gen) for L in (Lq, Lk, Lk))
+    keep = attn_bwd_mask(B, Lk, c["ext"]) if c["masked"] else None
+    if c["dead"]:
+        keep[B - 1] = False
+    full = torch.ones(B, Lk, dtype=torch.bool) if keep is None else keep
+    out = {}
+    if c["rel"]:
+        S = Lk
+        x = torch.randn(B * S, H * 64, generator=gen).to(torch.bfloat16).float()
+        lin = torch.nn.Linear(64, 8)
+        with torch.no_grad():
+            lin.weight.copy_(0.2 * torch.randn(8, 64, generator=gen))
+            lin.bias.copy_(0.1 * torch.randn(8, generator=gen))
+        gconst = 0.5 + torch.rand(H, generator=gen)
+        table = 2.0 * torch.randn(H, 2 * S - 1, generator=gen)
+        # models.wavlm._fold_gate's 130 floats, restated so that the reference needs no built library: the sums of
+        # weight rows 0-3 and 4-7, then the two bias sums (tests/test_cpu_host.py pins _fold_gate itself)
+        Wl, bl = lin.weight.detach().float(), lin.bias.detach().float()
+        gw = torch.cat([Wl[:4].sum(0), Wl[4:].sum(0), bl[:4].sum().reshape(1), bl[4:].sum().reshape(1)]).contiguous()
+        graw = (torch.einsum("nhd,od->nho", x.view(B * S, H, 64), lin.weight.detach()) + lin.bias.detach())
+        graw = graw.reshape(B * S, H * 8).to(torch.bfloat16).float()
+        gate = attn_fwd_gate64("gx", B, H, S, x=x, gw=gw, gconst=gconst)[0].float().reshape(B * H, S)
+        g64, dg = attn_fwd_gate64(c["src"], B, H, S, gate=gate, graw=graw, x=x, gw=gw, gconst=gconst)
+        out = dict(table=table, gconst=gconst, gw=gw, x=x, graw=graw, gate=gate, g64=g64, dg=dg)
+    if kind == "faint":
+        q = q * ATTN_FWD_FAINT
+    if kind == "edges":
+        w = (torch.randint(0, 2, (64,), generator=gen).float() * 2.0 - 1.0) / 8.0
+        live = [b for b in range(B) if full[b].any()]
+        if not c["rel"]:
+            q = ATTN_EDGE_QSTD * q + ATTN_EDGE_QW * w
+            for b in live:
+                ek = _attn_edge_keys(full[b], Lk)
+                beta = max(0.0, 8.0 / ATTN_EDGE_QW * math.log(ATTN_EDGE_MASS * int(full[b].sum()) / len(ek)))
+                k[b, ek] += beta * w
+                k[b, (~full[b]).nonzero().flatten()] += beta * w
+        else:
+            q = ATTN_EDGE_QSTD * q
+        if c["rel"] and Lk >= 4:
+            S = Lk
+            rel = attn_rel_index(S)
+            g64 = out["g64"]
+            base = 0.125 * torch.einsum("bihd,bkhd->bhik", q.double(), k.double())
+            base = (base + g64[..., None] * table.double()[:, rel][None]).masked_fill(~full[:, None, None, :],
+                                                                                    float("-inf"))
+            offs = sorted({o for a in ATTN_REL_SPIKES + (S - 1,) for o in (a, -a) if a <= S - 1} | {0})
+            spike = torch.zeros(2 * S - 1)
+            spike[[o + S - 1 for o in offs]] = 1.0
+            M = spike[rel][None, None].double()
+            h = _bisect(lambda t: _median_mass(base + t * g64[..., None] * M, M), 32.0, ATTN_REL_SPIKE_MASS)
+            base = base + h * g64[..., None] * M
+            # the last kept key of every entry: + 8 w on the key and alpha_i w on query i, alpha_i >= ATTN_REL_QW_MIN
+            # solved per row so that the key holds ATTN_REL_LAST_MASS of the row (more where 4 w already gives more)
+            E = torch.zeros(B, S, dtype=torch.float64)
+            for b in live:
+                E[b, int(full[b].nonzero().max())] = 1.0
+            E = E[:, None, None, :]
+            cw = 0.125 * torch.einsum("bkhd,d->bhk", k.double(), w.double())[:, :, None, :] + E
+            lo = torch.full(base.shape[:3], ATTN_REL_QW_MIN, dtype=torch.float64)
+            hi = torch.full_like(lo, ATTN_REL_QW_MAX)
+            for _ in range(14):
+                mid = 0.5 * (lo + hi)
+                low = (torch.softmax(base + mid[..., None] * cw, -1) * E).sum(-1) < ATTN_REL_LAST_MASS
+                lo, hi = torch.where(low, mid, lo), torch.where(low, hi, mid)
+            q = q + hi.float().transpose(1, 2)[..., None] * w
+            for b in live:
+                k[b, int(full[b].nonzero().max())] += 8.0 * w
+            for b in range(B):      # a masked key, were it kept, would outweigh the last key e^alpha times before the bias
+                k[b, (~full[b]).nonzero().flatten()] += 16.0 * w
+            out["table"] = table + h * spike
+    flat = lambda t, L: rnd(t).reshape(B, L, H * 64)  # noqa: E731
+    out.update(q=flat(q, Lq), k=flat(k, Lk), v=flat(v, Lk), keep=keep, drop=drop)
+    return out
+
+
+@functools.lru_cache(maxsize=6)
+def attn_fwd_case_ref(cid, kind):
+    """(AttnFwdRef, units, (O, LSE) of the emulation) of a case's family on its inputs. Built once, never modified."""
+    c = {x["id"]: x for x in attn_fwd_cases()}[cid]
+    x = attn_fwd_case_inputs(cid, kind)
+    q, k, v = (attn_heads(x[n], c["B"], c["H"]) for n in ("q", "k", "v"))
+    p = attn_p32(c["p"])
+    g, tb = (x["g64"], x["table"]) if c["rel"] else (None, None)
+    r = attn_fwd_terms64(q, k, v, x["keep"], x["drop"], p, 0.125, g, x.get("dg"), tb)
+    eo, el, trip = attn_fwd_emulate(c["family"], q, k, v, x["keep"], x["drop"], p, 0.125, g, tb)
+    return r, attn_fwd_units(c["family"], r, q, k, v, 0.125, "either" if c["g8"] else trip), (eo, el)
