@@ -7,6 +7,8 @@
 // residual blocks and feature-projection/encoder LayerNorms (HF modeling_wavlm.py:102, 313-317, 405).
 // backward: from dout (f32): ds (f32, the residual-branch gradient), dy = drop'(ds) in T for the
 // producing GEMM, dgamma/dbeta and dfilm_scale/dfilm_shift accumulated with atomics (caller zeroes).
+// Also the row LayerNorm + GELU kernels of the WavLM-Large conv feature extractor (conv0_ln_gelu, ln_gelu_fwd; HF
+// modeling_wavlm.py:696-720), which share the forward's row layout and reductions.
 #include "common.h"
 
 namespace fddm {
@@ -491,9 +493,170 @@ __global__ void __launch_bounds__(1024) ln_fold_kernel(LnFold f) {
   }
 }
 
+// ---- the "layer" conv feature extractor of the WavLM-Large family (HF modeling_wavlm.py:696-720): every conv layer
+// is Conv1d(bias) -> LayerNorm over the channels of each frame -> GELU. Both kernels keep ln_fwd_kernel's shape: one
+// wave per row, 8 consecutive channels per lane (d <= 512), centred two-pass statistics in registers, wave_sum_v.
+template <typename OT>
+__device__ __forceinline__ float ln_gelu_act(float z) {
+  if constexpr (sizeof(OT) == 2) return gelu_bf16out(z);  // rounded to bf16 next: the frozen encoder's epilogue form
+  else return gelu_f(z);
+}
+
+// out = gelu(LN(x) gamma + beta), rows of d <= 512 (conv layers 1-6: the GEMM's plain-store output). In place allowed:
+// a lane stores only the 8 elements it loaded.
+template <typename XT, typename OT>
+__global__ void __launch_bounds__(256) ln_gelu_fwd_kernel(const XT* xin, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, OT* out, long N, long d,
+                                                          float eps) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform
+  if (row >= N) return;
+  const long nch = d / 8;
+  const bool act = lane < nch;
+  const long c0 = min((long)lane, nch - 1) * 8;  // idle lanes load the last chunk again and contribute zeros
+  float v[8], gm[8], bt[8];
+  ld8<XT>(xin + row * d + c0, v);
+  ld8<float>(gamma + c0, gm);
+  ld8<float>(beta + c0, bt);
+  float sum = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    v[e] = act ? v[e] : 0.f;
+    sum += v[e];
+  }
+  const float mean = wave_sum_v(sum) / (float)d;
+  float sq = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float t = act ? v[e] - mean : 0.f;
+    sq += t * t;
+  }
+  const float rstd = 1.f / sqrtf(wave_sum_v(sq) / (float)d + eps);
+  if (act) {
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = ln_gelu_act<OT>((v[e] - mean) * rstd * gm[e] + bt[e]);
+    st8<OT>(out + row * d + c0, o);
+  }
+}
+
+// conv layer 0 (1 -> C channels, 10 taps) + bias + LayerNorm over the C channels of the frame + GELU. A workgroup
+// stages the samples of C0L_FRAMES frames in LDS; a lane keeps its 8 channels' taps, bias and affine in registers
+// (104 VGPRs) across the frames of its wave and reads each sample as an LDS broadcast. The conv is computed directly
+// (bias first, then ten FMAs in tap order), so a frame of exact zeros yields the bias vector exactly and the
+// statistics are those of the values that are normalised — no closed form from the window.
+constexpr int C0L_FRAMES = 64;
+template <typename OT>
+__global__ void __launch_bounds__(256) conv0_ln_gelu_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                            const float* __restrict__ bias,
+                                                            const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, OT* __restrict__ out,
+                                                            long nsamp, long T0, int C, int S, float eps) {
+  constexpr int K = 10;
+  extern __shared__ float c0l_xs[];
+  const long b = blockIdx.y;
+  const long t0 = (long)blockIdx.x * C0L_FRAMES;
+  const int nf = (int)min((long)C0L_FRAMES, T0 - t0);
+  const int span = (nf - 1) * S + K;  // t0 S + span <= (T0 - 1) S + K <= nsamp (checked by the host entry)
+  for (int i = threadIdx.x; i < span; i += 256) c0l_xs[i] = x[b * nsamp + t0 * S + i];
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nch = C / 8;
+  const bool act = lane < nch;
+  const int c0 = min(lane, nch - 1) * 8;
+  float wk[8][K], bs[8], gm[8], bt[8];
+  {
+    float t[8 * K];  // the lane's 8 rows of w are 80 consecutive floats
+#pragma unroll
+    for (int q = 0; q < 8 * K; q += 8) ld8<float>(w + (long)c0 * K + q, *(float(*)[8])(t + q));
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int k = 0; k < K; ++k) wk[e][k] = t[e * K + k];
+  }
+  ld8<float>(bias + c0, bs);
+  ld8<float>(gamma + c0, gm);
+  ld8<float>(beta + c0, bt);
+  __syncthreads();
+  const float inv = 1.f / (float)C;
+  for (int f = wv; f < nf; f += 4) {
+    float xv[K], y[8];
+#pragma unroll
+    for (int k = 0; k < K; ++k) xv[k] = c0l_xs[f * S + k];
+    float sum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float a = bs[e];
+#pragma unroll
+      for (int k = 0; k < K; ++k) a = fmaf(wk[e][k], xv[k], a);
+      y[e] = act ? a : 0.f;
+      sum += y[e];
+    }
+    const float mean = wave_sum_v(sum) * inv;
+    float sq = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float t = act ? y[e] - mean : 0.f;
+      sq += t * t;
+    }
+    const float rstd = 1.f / sqrtf(wave_sum_v(sq) * inv + eps);
+    if (act) {
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = ln_gelu_act<OT>((y[e] - mean) * rstd * gm[e] + bt[e]);
+      st8<OT>(out + ((b * T0 + t0 + f) * C + c0), o);
+    }
+  }
+}
+
 }  // namespace fddm
 
 using namespace fddm;
+
+FDDM_API int fddm_conv0_ln_gelu(int out_dtype, const float* x, const float* w, const float* bias, const float* gamma,
+                                const float* beta, void* out, long B, long nsamp, long T0, int C, int K, int S,
+                                float eps, void* hs) {
+  if (K != 10 || C <= 0 || C % 8 || C > 512 || S < 1 || S > 16) return (int)hipErrorInvalidValue;
+  if (out_dtype != FDDM_F32 && out_dtype != FDDM_BF16) return (int)hipErrorInvalidValue;
+  if (!x || !w || !bias || !gamma || !beta || !out) return (int)hipErrorInvalidValue;
+  if ((((uintptr_t)w | (uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15) ||
+      ((uintptr_t)x & 3))
+    return (int)hipErrorInvalidValue;  // 16-B vector accesses (x: scalar loads)
+  if (B < 0 || T0 < 0 || B > 65535 || (T0 > 0 && (T0 - 1) * S + K > nsamp)) return (int)hipErrorInvalidValue;
+  if (B == 0 || T0 == 0) return 0;
+  dim3 grid((unsigned)((T0 + C0L_FRAMES - 1) / C0L_FRAMES), (unsigned)B);
+  const size_t lds = ((C0L_FRAMES - 1) * S + K) * sizeof(float);
+  hipStream_t s = (hipStream_t)hs;
+  if (out_dtype == FDDM_BF16)
+    hipLaunchKernelGGL((conv0_ln_gelu_kernel<bf16_t>), grid, dim3(256), lds, s, x, w, bias, gamma, beta, (bf16_t*)out,
+                       nsamp, T0, C, S, eps);
+  else
+    hipLaunchKernelGGL((conv0_ln_gelu_kernel<float>), grid, dim3(256), lds, s, x, w, bias, gamma, beta, (float*)out,
+                       nsamp, T0, C, S, eps);
+  return (int)hipGetLastError();
+}
+
+FDDM_API int fddm_ln_gelu_fwd(int x_dtype, int out_dtype, const void* x, const float* gamma, const float* beta,
+                              void* out, long N, long d, float eps, void* hs) {
+  if (d <= 0 || d > 512 || d % 8) return (int)hipErrorInvalidValue;
+  if ((x_dtype != FDDM_F32 && x_dtype != FDDM_BF16) || (out_dtype != FDDM_F32 && out_dtype != FDDM_BF16))
+    return (int)hipErrorInvalidValue;
+  if (!x || !gamma || !beta || !out) return (int)hipErrorInvalidValue;
+  if ((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15)) return (int)hipErrorInvalidValue;
+  if (x == out && x_dtype != out_dtype) return (int)hipErrorInvalidValue;  // in place: same element size only
+  if (N < 0) return (int)hipErrorInvalidValue;
+  if (N == 0) return 0;
+  dim3 grid((unsigned)((N + 3) / 4));
+  hipStream_t s = (hipStream_t)hs;
+  if (x_dtype == FDDM_F32 && out_dtype == FDDM_F32)
+    hipLaunchKernelGGL((ln_gelu_fwd_kernel<float, float>), grid, dim3(256), 0, s, (const float*)x, gamma, beta, (float*)out, N, d, eps);
+  else if (x_dtype == FDDM_F32)
+    hipLaunchKernelGGL((ln_gelu_fwd_kernel<float, bf16_t>), grid, dim3(256), 0, s, (const float*)x, gamma, beta, (bf16_t*)out, N, d, eps);
+  else if (out_dtype == FDDM_F32)
+    hipLaunchKernelGGL((ln_gelu_fwd_kernel<bf16_t, float>), grid, dim3(256), 0, s, (const bf16_t*)x, gamma, beta, (float*)out, N, d, eps);
+  else
+    hipLaunchKernelGGL((ln_gelu_fwd_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)x, gamma, beta, (bf16_t*)out, N, d, eps);
+  return (int)hipGetLastError();
+}
 
 // x_dtype/y_dtype/out_dtype: FDDM_F32 / FDDM_BF16. y may be null. Outputs may be null.
 FDDM_API int fddm_ln_fwd(int x_dtype, int y_dtype, int out_dtype, const void* x, const void* y, const float* gamma,

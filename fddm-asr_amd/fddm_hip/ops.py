@@ -359,6 +359,47 @@ def conv0_gn_gelu(wave, w, gamma, beta, out_dtype, C, K, S, eps=1e-5):
     return out
 
 
+def conv0_ln_gelu(wave, w, bias, gamma, beta, out_dtype, C, K, S, eps=1e-5, out=None):
+    """Conv layer 0 of the WavLM-Large family: conv (w [C, K], bias) + LayerNorm over the C channels of every frame +
+    GELU: wave [B, nsamp] f32 -> [B, T0, C] (f32 / bf16; written into `out`, contiguous, if given)."""
+    _chk(wave.dim() == 2 and wave.is_contiguous() and wave.dtype == torch.float32,
+         "conv0: wave is contiguous f32 [B, nsamp]")
+    _chk(K == 10 and C % 8 == 0 and 0 < C <= 512, "conv0_ln: kernel width 10, C a multiple of 8 up to 512")
+    _chk(w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (C, K), "conv0: w is contiguous f32 [C, K]")
+    for t in (bias, gamma, beta):
+        _chk(t.dtype == torch.float32 and t.numel() == C and t.is_contiguous(), "conv0_ln: bias, gamma and beta are f32 [C]")
+    _chk(out_dtype in (torch.float32, torch.bfloat16), "conv0: f32 or bf16 output")
+    B, nsamp = wave.shape
+    _chk(nsamp >= K, "conv0: an utterance shorter than the kernel")
+    T0 = (nsamp - K) // S + 1
+    if out is None:
+        out = torch.empty(B, T0, C, device=wave.device, dtype=out_dtype)
+    _chk(out.is_contiguous() and tuple(out.shape) == (B, T0, C) and out.dtype == out_dtype,
+         "conv0_ln: out is contiguous [B, T0, C] of out_dtype")
+    call("fddm_conv0_ln_gelu", code(out), ptr(wave), ptr(w), ptr(bias), ptr(gamma), ptr(beta), ptr(out), B, nsamp, T0,
+         C, K, S, float(eps), stream())
+    return out
+
+
+def ln_gelu_fwd(x2d, gamma, beta, out=None, out_dtype=None, eps=1e-5):
+    """gelu(LayerNorm(x) gamma + beta) over the rows of x2d [N, d] (f32 / bf16; d % 8 == 0, d <= 512). out: a
+    contiguous [N, d] tensor (x2d itself for in place), or None for a new one of out_dtype (default x2d's)."""
+    _chk(x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype in (torch.float32, torch.bfloat16),
+         "ln_gelu: x is contiguous f32 / bf16 [N, d]")
+    N, d = x2d.shape
+    _chk(d % 8 == 0 and 0 < d <= 512, "ln_gelu: d a multiple of 8 up to 512")
+    for t in (gamma, beta):
+        _chk(t.dtype == torch.float32 and t.numel() == d and t.is_contiguous(), "ln_gelu: gamma and beta are f32 [d]")
+    if out is None:
+        out = torch.empty(N, d, device=x2d.device, dtype=out_dtype or x2d.dtype)
+    _chk(out.is_contiguous() and tuple(out.shape) == (N, d) and out.dtype in (torch.float32, torch.bfloat16),
+         "ln_gelu: out is contiguous f32 / bf16 [N, d]")
+    _chk(out.data_ptr() != x2d.data_ptr() or out.dtype == x2d.dtype, "ln_gelu: in place needs equal dtypes")
+    call("fddm_ln_gelu_fwd", code(x2d), code(out), ptr(x2d), ptr(gamma), ptr(beta), ptr(out), N, d, float(eps),
+         stream())
+    return out
+
+
 def wavlm_gate(x2d, W, bias, cst, B, S, H):
     """Gated relative-position gate: x2d [B*S, E] (f32 / bf16), W [8, E/H] f32, bias [8], cst [H] -> [B*H, S] f32."""
     _chk(x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype in (torch.float32, torch.bfloat16),

@@ -4,8 +4,10 @@ Same constructor and forward contract: forward(waveforms[B,T], lengths=None) ->
 (features [B,S,d_model], feat_mask or None, pooled or None); attributes backbone / proj / use_proj /
 pooling; state_dict keys `backbone.<HF WavLM names>` and `proj.*`.
 
-`wavlm_name` may be a local HF-format directory (loaded), a dict of WavLMConfig geometry overrides,
-or a hub name (no network here: WavLM-base geometry with random init, as the benchmark specifies).
+`wavlm_name` may be a local HF-format directory (loaded strictly; both the WavLM-base and the WavLM-Large
+family, e.g. a copy of microsoft/wavlm-large: config.json + model.safetensors / pytorch_model.bin), a dict
+of WavLMConfig geometry overrides (models.wavlm.WAVLM_LARGE is the published large geometry), or a hub name
+(nothing is downloaded: WavLM-base geometry with random init, as the benchmark specifies).
 The encoder is frozen and runs forward-only on libfddm_hip; its output is returned without autograd
 history (the reference's encoder.proj receives a gradient it never applies, train.py:543).
 """
@@ -30,7 +32,9 @@ class AcousticEncoder(nn.Module):
         super().__init__()
         if isinstance(wavlm_name, str) and not wavlm_name.startswith("/") and not wavlm_name.startswith("."):
             logging.getLogger(__name__).warning(
-                "AcousticEncoder: %r is a hub name; no network -> WavLM-base geometry, random init", wavlm_name)
+                "AcousticEncoder: %r is a hub name; nothing is downloaded -> WavLM-base geometry, random init "
+                "(pass a local directory with config.json + weights, WavLM-base or WavLM-Large family, to load one)",
+                wavlm_name)
         self.backbone = WavLMModel.from_pretrained(wavlm_name)
         hidden = self.backbone.config.hidden_size
         if freeze:

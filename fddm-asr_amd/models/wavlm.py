@@ -1,11 +1,17 @@
 """Frozen WavLM encoder (forward only) on libfddm_hip.
 
-Parameter tree and state_dict names are those of transformers' WavLMModel (post-LN "group"
-geometry, HF modeling_wavlm.py:37-1088), so HF checkpoints of that family load with
-load_state_dict. The forward is a fixed kernel sequence per utterance batch:
-  conv0+GroupNorm+GELU -> 6 x implicit-GEMM conv+GELU -> LN -> Linear -> grouped positional
-  implicit-GEMM conv+GELU -> +x -> LN -> 12 x [gate, QKV GEMM, rel-bias flash attention, out GEMM,
-  +x LN, FF GEMM(GELU), FF GEMM, +x LN]
+Parameter tree and state_dict names are those of transformers' WavLMModel (HF modeling_wavlm.py:37-1088), so HF
+checkpoints load with load_state_dict. Both families HF ships are built:
+  * WavLM-base (feat_extract_norm="group", no conv bias, post-LN layers):
+      conv0+GroupNorm+GELU -> 6 x implicit-GEMM conv+GELU -> LN -> Linear -> grouped positional
+      implicit-GEMM conv+GELU -> +x -> LN -> 12 x [gate, QKV GEMM, rel-bias flash attention, out GEMM,
+      +x LN, FF GEMM(GELU), FF GEMM, +x LN]
+  * WavLM-Large (feat_extract_norm="layer", conv_bias, do_stable_layer_norm: pre-LN layers, HF:339-373, 450-522,
+    696-720):
+      conv0+bias+row LN+GELU -> 6 x [implicit-GEMM conv+bias, row LN+GELU] -> LN -> Linear -> positional conv+GELU ->
+      24 x [h+ -> LN, gate, QKV GEMM, attention, out GEMM, h+ -> LN, FF GEMM(GELU), FF GEMM] -> h+ -> encoder LN
+    with the residual stream h in f32: every "h+ -> LN" is one ln_fwd launch that returns the sum and the next
+    normalised input.
 All activations are channels-last [B, T, C] in the compute dtype.
 """
 from __future__ import annotations
@@ -40,6 +46,12 @@ WAVLM_BASE = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12,
                   mask_time_prob=0.05, hidden_act="gelu", feat_extract_activation="gelu")
 
 
+# microsoft/wavlm-large (its config.json): the "layer" feature extractor with conv bias and pre-LN transformer layers
+WAVLM_LARGE = dict(WAVLM_BASE, hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096,
+                   conv_bias=True, feat_extract_norm="layer", do_stable_layer_norm=True)
+CONV_LN_EPS = 1e-5      # nn.LayerNorm's default: the conv LayerNorms do not take config.layer_norm_eps (HF:704)
+
+
 def wavlm_config(**over) -> SimpleNamespace:
     cfg = dict(WAVLM_BASE)
     cfg.update({k: v for k, v in over.items() if k in WAVLM_BASE or k in ("mask_feature_prob",)})
@@ -54,8 +66,16 @@ class WavLMModel(nn.Module):
     def __init__(self, config: SimpleNamespace):
         super().__init__()
         c = config
-        if c.feat_extract_norm != "group" or c.do_stable_layer_norm or c.conv_bias:
-            raise NotImplementedError("only the post-LN 'group' WavLM geometry (WavLM-base family) is built")
+        sw = (c.feat_extract_norm, bool(c.conv_bias), bool(c.do_stable_layer_norm))
+        if sw not in (("group", False, False), ("layer", True, True)):
+            raise NotImplementedError(
+                f"feat_extract_norm={sw[0]!r}, conv_bias={sw[1]}, do_stable_layer_norm={sw[2]}: only the two WavLM "
+                "families transformers ships are built: ('group', False, False) (WavLM-base: GroupNorm on conv layer "
+                "0, post-LN layers) and ('layer', True, True) (WavLM-Large: LayerNorm conv stack with bias, pre-LN "
+                "layers)")
+        self.stable_ln = sw[0] == "layer"
+        if self.stable_ln and (max(c.conv_dim) > 512 or any(cd_ % 8 for cd_ in c.conv_dim)):
+            raise NotImplementedError("the 'layer' conv stack needs conv_dim multiples of 8 up to 512")
         if c.hidden_size // c.num_attention_heads != 64:
             raise NotImplementedError("head_dim must be 64")
         self.config = c
@@ -64,8 +84,10 @@ class WavLMModel(nn.Module):
         cin = 1
         for i, (co, k, s) in enumerate(zip(c.conv_dim, c.conv_kernel, c.conv_stride)):
             layer = _Sub()
-            layer.conv = nn.Conv1d(cin, co, kernel_size=k, stride=s, bias=False)
-            if i == 0:
+            layer.conv = nn.Conv1d(cin, co, kernel_size=k, stride=s, bias=bool(c.conv_bias))
+            if self.stable_ln:
+                layer.layer_norm = nn.LayerNorm(co, eps=CONV_LN_EPS, elementwise_affine=True)
+            elif i == 0:
                 layer.layer_norm = nn.GroupNorm(co, co, affine=True)
             fe.conv_layers.append(layer)
             cin = co
@@ -136,6 +158,11 @@ class WavLMModel(nn.Module):
             P["w0"] = cl[0].conv.weight.detach().float().reshape(c.conv_dim[0], -1).contiguous()
             P["gn"] = (cl[0].layer_norm.weight.detach().float().contiguous(), cl[0].layer_norm.bias.detach().float().contiguous())
             P["conv"] = [T(cl[i].conv.weight.permute(0, 2, 1)) for i in range(1, len(cl))]
+            if self.stable_ln:
+                P["b0"] = cl[0].conv.bias.detach().float().contiguous()
+                P["conv_b"] = [cl[i].conv.bias.detach().float().contiguous() for i in range(1, len(cl))]
+                P["conv_ln"] = [(cl[i].layer_norm.weight.detach().float().contiguous(),
+                                 cl[i].layer_norm.bias.detach().float().contiguous()) for i in range(1, len(cl))]
             fp = self.feature_projection
             P["fp_ln"] = (fp.layer_norm.weight.detach().float(), fp.layer_norm.bias.detach().float())
             P["fp"] = (T(fp.projection.weight), fp.projection.bias.detach().float())
@@ -188,11 +215,15 @@ class WavLMModel(nn.Module):
     # the benchmark's probe of that dominant launch an ordinary timed launch: fddm_hip/graphs.py)
     @torch.no_grad()
     def stage_conv0(self, wave: torch.Tensor) -> torch.Tensor:
-        """conv layer 0 + GroupNorm + GELU (HF:723-744) -> [B, T0, C] compute dtype."""
+        """conv layer 0 + GroupNorm + GELU (HF:723-744), or + bias + LayerNorm + GELU (HF:696-720) -> [B, T0, C]
+        compute dtype."""
         c = self.config
         cd = rt.compute_dtype()
         P = self._prepared(cd)
         wave = wave.float().contiguous()
+        if self.stable_ln:
+            return ops.conv0_ln_gelu(wave, P["w0"], P["b0"], P["gn"][0], P["gn"][1], cd, c.conv_dim[0],
+                                     c.conv_kernel[0], c.conv_stride[0], eps=CONV_LN_EPS)
         return ops.conv0_gn_gelu(wave, P["w0"], P["gn"][0], P["gn"][1], cd, c.conv_dim[0], c.conv_kernel[0],
                                  c.conv_stride[0])
 
@@ -203,7 +234,8 @@ class WavLMModel(nn.Module):
 
     @torch.no_grad()
     def stage_conv1(self, h: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """conv layer 1 + GELU as an implicit GEMM (HF:747-782), the step's largest MFMA launch."""
+        """conv layer 1 + GELU as an implicit GEMM (HF:747-782), the step's largest MFMA launch; in the 'layer' family
+        the GEMM adds the bias and stores, and one row LayerNorm + GELU pass follows in place."""
         return self._conv(h, 1, out)
 
     def _conv(self, h, i, out=None):
@@ -228,7 +260,11 @@ class WavLMModel(nn.Module):
             out = torch.empty(B, Tout, co, device=h.device, dtype=h.dtype)
         with rt.probe(f"wavlm.conv{i}"):
             ops.conv1d_gemm(h, P["conv"][i - 1], out, lda=cin, sAb=T * cin, Tin=T, Cg=cin, cstride=s, cpad=0, Bn=B,
-                            Tout=Tout, N=co, K=k * cin, gelu=True)
+                            Tout=Tout, N=co, K=k * cin, bias=P["conv_b"][i - 1] if self.stable_ln else None,
+                            gelu=not self.stable_ln)
+        if self.stable_ln:
+            g, b = P["conv_ln"][i - 1]
+            ops.ln_gelu_fwd(out.view(B * Tout, co), g, b, out=out.view(B * Tout, co), eps=CONV_LN_EPS)
         return out
 
     @torch.no_grad()
@@ -246,7 +282,7 @@ class WavLMModel(nn.Module):
 
     @torch.no_grad()
     def stage_rest(self, h: torch.Tensor, feat_keep: torch.Tensor | None = None) -> torch.Tensor:
-        """conv layers 2..6, feature projection, positional conv, 12 transformer layers -> [B, S, E].
+        """conv layers 2..6, feature projection, positional conv, the transformer layers -> [B, S, E].
         feat_keep (uint8 [B, S], != 0 keeps; None: no padding): HF's attention_mask path — padded frames are zeroed
         after the feature projection and before the positional conv (modeling_wavlm.py:399-402) and are no keys in any
         layer's attention (:198); their output rows are whatever the layers leave there (HF does not zero them)."""
@@ -278,23 +314,17 @@ class WavLMModel(nn.Module):
         else:
             ops.conv1d_gemm(x, P["pos"][0], pos, lda=E, sAb=S * E, Tin=S, Cg=Cg, cstride=1, cpad=kp // 2, Bn=B,
                             Tout=S, N=Cg, K=kp * Cg, groups=G, bias=P["pos"][1], gelu=True)
+        table = rt.relbias_table(S, self.encoder.layers[0].attention.rel_attn_embed.weight, c.num_buckets,
+                                 c.max_bucket_distance)
+        if self.stable_ln:
+            return self._layers_stable(x, pos, P, table, feat_keep, key_len, B, S).view(B, S, E)
         xn = torch.empty_like(x)
         ops.ln_fwd(x, pos, P["enc_ln"][0], P["enc_ln"][1], out_t=xn, eps=eps)
         x = xn
-        table = rt.relbias_table(S, self.encoder.layers[0].attention.rel_attn_embed.weight, c.num_buckets,
-                                 c.max_bucket_distance)
         for Lp in P["layers"]:
             qkv = ops.linear(x, Lp["qkv"], Lp["bqkv"], out_dtype=cd)
             o = torch.empty(B * S, E, device=dev, dtype=cd)
-            if cd == torch.bfloat16 and GATE_MODE == "x":
-                ops.attn_fwd_relgate_x(qkv, qkv[:, E:], qkv[:, 2 * E:], o, x, Lp["gw"], Lp["gru"][2], table, B, H, S,
-                                       key_keep=feat_keep, key_len=key_len)
-            elif cd == torch.bfloat16 and GATE_MODE == "cols" and feat_keep is None:
-                ops.attn_fwd_relgate(qkv, qkv[:, E:], qkv[:, 2 * E:], o, qkv[:, 3 * E:], Lp["gru"][2], table, B, H, S)
-            else:   # fp32; or a masked batch under the "cols" / "separate" gate modes: the general entry
-                gate = ops.wavlm_gate(x, Lp["gru"][0], Lp["gru"][1], Lp["gru"][2], B, S, H)
-                ops.attn_fwd(qkv, qkv[:, E:], qkv[:, 2 * E:], o, None, B, H, S, S, gate=gate, table=table,
-                             key_keep=feat_keep, key_len=key_len)
+            o = self._attention(qkv, o, x, Lp, table, feat_keep, key_len, B, S)
             y = ops.linear(o, Lp["o"][0], Lp["o"][1], out_dtype=cd)
             x1 = torch.empty_like(x)
             ops.ln_fwd(x, y, Lp["ln1"][0], Lp["ln1"][1], out_t=x1, eps=eps)
@@ -303,6 +333,50 @@ class WavLMModel(nn.Module):
             x = torch.empty_like(x1)
             ops.ln_fwd(x1, y, Lp["ln2"][0], Lp["ln2"][1], out_t=x, eps=eps)
         return x.view(B, S, E)
+
+    def _attention(self, qkv, o, x, Lp, table, feat_keep, key_len, B, S):
+        """One layer's gated relative-position attention; x is the attention input the gate reads (HF:166-186)."""
+        c = self.config
+        E, H = c.hidden_size, c.num_attention_heads
+        cd = qkv.dtype
+        if cd == torch.bfloat16 and GATE_MODE == "x":
+            ops.attn_fwd_relgate_x(qkv, qkv[:, E:], qkv[:, 2 * E:], o, x, Lp["gw"], Lp["gru"][2], table, B, H, S,
+                                   key_keep=feat_keep, key_len=key_len)
+        elif cd == torch.bfloat16 and GATE_MODE == "cols" and feat_keep is None:
+            ops.attn_fwd_relgate(qkv, qkv[:, E:], qkv[:, 2 * E:], o, qkv[:, 3 * E:], Lp["gru"][2], table, B, H, S)
+        else:   # fp32; or a masked batch under the "cols" / "separate" gate modes: the general entry
+            gate = ops.wavlm_gate(x, Lp["gru"][0], Lp["gru"][1], Lp["gru"][2], B, S, H)
+            ops.attn_fwd(qkv, qkv[:, E:], qkv[:, 2 * E:], o, None, B, H, S, S, gate=gate, table=table,
+                         key_keep=feat_keep, key_len=key_len)
+        return o
+
+    def _layers_stable(self, x, pos, P, table, feat_keep, key_len, B, S):
+        """The pre-LN encoder (HF WavLMEncoderStableLayerNorm :450-522, its layer :339-373): h = x + pos with no
+        LayerNorm; per layer h += attn(layer_norm(h)), h += ff(final_layer_norm(h)); encoder.layer_norm after the last
+        layer. The residual stream h is f32 (save_s, updated in place: a lane rewrites only what it loaded); every
+        site is one ln_fwd launch giving h + branch and LN(h + branch) for the next consumer."""
+        c = self.config
+        cd = x.dtype
+        E = c.hidden_size
+        eps = c.layer_norm_eps
+        layers = P["layers"]
+        h = torch.empty(B * S, E, device=x.device, dtype=torch.float32)
+        xn = torch.empty_like(x)
+        ops.ln_fwd(x, pos, layers[0]["ln1"][0], layers[0]["ln1"][1], out_t=xn, save_s=h, eps=eps)
+        for i, Lp in enumerate(layers):
+            qkv = ops.linear(xn, Lp["qkv"], Lp["bqkv"], out_dtype=cd)
+            o = torch.empty(B * S, E, device=x.device, dtype=cd)
+            self._attention(qkv, o, xn, Lp, table, feat_keep, key_len, B, S)
+            y = ops.linear(o, Lp["o"][0], Lp["o"][1], out_dtype=cd)
+            x1 = torch.empty_like(xn)
+            ops.ln_fwd(h, y, Lp["ln2"][0], Lp["ln2"][1], out_t=x1, save_s=h, eps=eps)
+            hh = ops.linear(x1, Lp["f1"][0], Lp["f1"][1], out_dtype=cd, epi=ops.EPI_GELU_ONLY)
+            y = ops.linear(hh, Lp["f2"][0], Lp["f2"][1], out_dtype=cd)
+            last = i + 1 == len(layers)
+            g, b = P["enc_ln"] if last else layers[i + 1]["ln1"]
+            xn = torch.empty_like(x1)
+            ops.ln_fwd(h, y, g, b, out_t=xn, save_s=None if last else h, eps=eps)
+        return xn
 
     @torch.no_grad()
     def forward_hidden(self, wave: torch.Tensor, attention_mask: torch.Tensor | None = None) -> torch.Tensor:

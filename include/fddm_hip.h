@@ -89,6 +89,20 @@ int fddm_conv0_gn_gelu(int out_dtype, const float* x, const float* w, const floa
                        double* ws, void* out, long B, long nsamp, long T0, int C, int K, int S, float eps,
                        void* hip_stream);
 
+/* ---- conv layer 0 + bias + per-frame LayerNorm over the C channels + GELU (the "layer" feature extractor of the
+ *      WavLM-Large family, HF modeling_wavlm.py:696-720): x [B][nsamp] f32 -> out [B][T0][C] f32 / bf16.
+ *      K == 10, C % 8 == 0, C <= 512, 1 <= S <= 16, (T0 - 1) S + K <= nsamp; w [C][K], bias, gamma, beta [C] f32 and
+ *      out 16-B aligned, none null. Otherwise hipErrorInvalidValue, before anything is launched. */
+int fddm_conv0_ln_gelu(int out_dtype, const float* x, const float* w, const float* bias, const float* gamma,
+                       const float* beta, void* out, long B, long nsamp, long T0, int C, int K, int S, float eps,
+                       void* hip_stream);
+
+/* ---- row LayerNorm (affine, biased variance) + GELU of conv layers 1-6 of that family: x, out [N][d] f32 / bf16
+ *      (out may be x when the dtypes agree), d % 8 == 0, d <= 512, every pointer 16-B aligned and non-null.
+ *      Otherwise hipErrorInvalidValue, before anything is launched. */
+int fddm_ln_gelu_fwd(int x_dtype, int out_dtype, const void* x, const float* gamma, const float* beta, void* out,
+                     long N, long d, float eps, void* hip_stream);
+
 /* ---- WavLM gated rel-pos gate [B*H][S]. HF modeling_wavlm.py:166-180. */
 int fddm_wavlm_gate(int dtype, const void* x, const float* W, const float* bias, const float* cst, float* gate, long B,
                     long S, int H, long E, void* hip_stream);
