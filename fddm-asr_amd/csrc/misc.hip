@@ -310,6 +310,7 @@ FDDM_API int fddm_rope_fwd(int out_dtype, const float* x, const float* cs, const
 FDDM_API int fddm_rope_bwd(const float* dy, const float* cs, const float* sn, float* dx, long N, long L, long d,
                            void* hs) {
   if (N <= 0) return 0;
+  if (d % 2) return (int)hipErrorInvalidValue;
   const long n = N * (d / 2);
   if (vec_ok(d, N, {dy, cs, sn, dx}))
     hipLaunchKernelGGL(rope_bwd_kernel, g1(N * (d / 8)), dim3(256), 0, (hipStream_t)hs, dy, cs, sn, dx, (int)N, (int)L,

@@ -178,9 +178,11 @@ __global__ void time_embed_kernel(const long* __restrict__ t, float* __restrict_
   float v = 0.f;
   if (k < 2 * half) {
     const long kk = k < half ? k : k - half;
-    // torch.linspace(start, end, steps): start + i * step with step = (end - start) / (steps - 1)
+    // torch.linspace(start, end, steps): start + i * step with step = (end - start) / (steps - 1); one step (d = 2,
+    // 3) returns its start, log 1 = 0, so the single frequency is 1 and not 1 / max_steps
     const float step = half > 1 ? log_max / (float)(half - 1) : 0.f;
-    const float lin = (kk < half / 2) ? (float)kk * step : log_max - (float)(half - 1 - kk) * step;
+    const float lin = half == 1 ? 0.f
+                                : (kk < half / 2) ? (float)kk * step : log_max - (float)(half - 1 - kk) * step;
     const float f = expf(-lin);
     const float a = (float)t[b] * f;
     v = k < half ? sinf(a) : cosf(a);

@@ -653,26 +653,79 @@ class LnPartials:
 
 
 # -------------------------------------------------------------------------------- small kernels
-def rope_fwd(x, cs, sn, out, L):
+_F32 = torch.float32
+
+
+def _chk_rope(name, x, cs, sn, out, L, out_dtypes):
+    """The shared preconditions of rope_fwd / rope_bwd: the kernels index every tensor as contiguous [N, d] /
+    [L, d] rows from a raw pointer, positions are r % L."""
+    _chk(x.dim() == 2 and x.dtype == _F32 and x.is_contiguous(), f"{name}: input is contiguous f32 [N, d]")
     N, d = x.shape
+    _chk(d % 2 == 0, f"{name}: d is even")
+    _chk(L >= 1, f"{name}: L >= 1")
+    _chk(out.shape == x.shape and out.is_contiguous() and out.dtype in out_dtypes,
+         f"{name}: output is contiguous [N, d], " + " or ".join(str(t)[6:] for t in out_dtypes))
+    for t in (cs, sn):
+        _chk(t.dim() == 2 and t.dtype == _F32 and t.is_contiguous() and t.shape[1] == d and t.shape[0] >= L,
+             f"{name}: cos and sin are contiguous f32 [>= L, d]")
+    _chk(x.device == out.device == cs.device == sn.device and x.is_cuda, f"{name}: every tensor on one GPU")
+    return N, d
+
+
+def rope_fwd(x, cs, sn, out, L):
+    """out = RoPE(x), row r at position r % L: x f32 [N, d] (d even), cs / sn f32 [>= L, d], out [N, d] f32 or bf16;
+    every tensor contiguous and on one device."""
+    N, d = _chk_rope("rope_fwd", x, cs, sn, out, L, (torch.float32, torch.bfloat16))
     call("fddm_rope_fwd", code(out), ptr(x), ptr(cs), ptr(sn), ptr(out), N, L, d, stream())
     return out
 
 
 def rope_bwd(dy, cs, sn, dx, L):
-    N, d = dy.shape
+    """dx += RoPE^T(dy): dy, dx f32 [N, d] (d even), cs / sn f32 [>= L, d]; every tensor contiguous and on one
+    device."""
+    N, d = _chk_rope("rope_bwd", dy, cs, sn, dx, L, (torch.float32,))
     call("fddm_rope_bwd", ptr(dy), ptr(cs), ptr(sn), ptr(dx), N, L, d, stream())
 
 
+def _chk_embed(name, tok, E, tb, tb_name, L, d, rows):
+    """The shared preconditions of embed_fwd / embed_bwd: E (or dE) [V, d] and tb (tbias or dtb) may be None where the
+    kernel allows it; rows: (name, [N, d] tensor or None, dtypes). Returns N, the token count."""
+    _chk(tok.dtype == torch.int64 and tok.is_contiguous(), f"{name}: tokens are contiguous int64")
+    N, dev = tok.numel(), tok.device
+    _chk(L >= 1, f"{name}: L >= 1")
+    _chk(E is None or (E.dim() == 2 and E.dtype == _F32 and E.is_contiguous() and E.shape[1] == d),
+         f"{name}: the table is contiguous f32 [V, d]")
+    _chk(tb is None or (tb.dim() == 2 and tb.dtype == _F32 and tb.is_contiguous() and tb.shape[1] == d
+                        and tb.shape[0] * L >= N), f"{name}: {tb_name} is contiguous f32 [>= ceil(N / L), d]")
+    for nm, t, dts in rows:
+        _chk(t is None or (tuple(t.shape) == (N, d) and t.is_contiguous() and t.dtype in dts),
+             f"{name}: {nm} is contiguous [N, d], " + " or ".join(str(x)[6:] for x in dts))
+    _chk(tok.is_cuda and all(t is None or t.device == dev for t in (E, tb) + tuple(r[1] for r in rows)),
+         f"{name}: every tensor on one GPU")
+    return N
+
+
 def embed_fwd(tok, E, tbias, out, out_t, L):
-    N = tok.numel()
+    """out[r] = E[tok[r]] + tbias[r // L] (f32; out_t: the same value in f32 / bf16; either may be None): tok int64 (N
+    of them), E f32 [V, d], tbias None or f32 [>= ceil(N / L), d], out / out_t [N, d]; every tensor contiguous and on
+    one device. Token ids outside [0, V) cannot be refused here: checking them needs their values, a device read
+    and a stream synchronisation on the step's critical path; they index E unchecked and are the caller's to
+    exclude."""
+    _chk(E is not None and E.dim() == 2, "embed_fwd: the table is contiguous f32 [V, d]")
     d = E.shape[1]
+    N = _chk_embed("embed_fwd", tok, E, tbias, "tbias", L, d,
+                   (("out", out, (_F32,)), ("out_t", out_t, (_F32, torch.bfloat16))))
     call("fddm_embed_fwd", code(out_t) if out_t is not None else F32, ptr(tok), ptr(E), ptr(tbias), ptr(out),
          ptr(out_t), N, L, d, stream())
 
 
 def embed_bwd(tok, dx, dE, dtb, L, pad_id):
-    N, d = dx.shape
+    """dE[tok[r]] += dx[r] for tok[r] != pad_id, dtb[r // L] += dx[r] (either may be None): tok int64 (N of them), dx
+    f32 [N, d], dE f32 [V, d], dtb f32 [>= ceil(N / L), d]; every tensor contiguous and on one device. Token ids
+    outside [0, V) are not checked (see embed_fwd)."""
+    _chk(dx is not None and dx.dim() == 2, "embed_bwd: dx is contiguous [N, d], float32")
+    d = dx.shape[1]
+    N = _chk_embed("embed_bwd", tok, dE, dtb, "dtb", L, d, (("dx", dx, (_F32,)),))
     call("fddm_embed_bwd", ptr(tok), ptr(dx), ptr(dE), ptr(dtb), N, L, d, pad_id, stream())
 
 
@@ -905,6 +958,23 @@ def small_linear(inp, Ws, bs, outs, outs2=None, act=0, aux=None, transpose_w=Fal
         _chk(W.dtype == torch.float32 and W.is_contiguous() and W.shape == W0.shape, "small_linear weights")
         _chk(o.dtype == torch.float32 and o.shape == (R, N) and o.stride(1) == 1 and o.stride(0) == N, "small_linear out")
     _chk(inp.dtype == torch.float32 and inp.stride(1) == 1, "small_linear input")
+    _chk(len(outs) == len(Ws), "small_linear: one output per weight set")
+    if bs is not None:
+        _chk(len(bs) == len(Ws), "small_linear: one bias per weight set")
+        for b in bs:
+            _chk(b is None or (b.dtype == torch.float32 and b.is_contiguous() and tuple(b.shape) == (N,)),
+                 "small_linear: biases are contiguous f32 [N]")
+    if act == 1:
+        _chk(outs2 is not None and len(outs2) == len(outs), "small_linear: act 1 writes silu into outs2, one per output")
+        for o2 in outs2:
+            _chk(o2.dtype == torch.float32 and tuple(o2.shape) == (R, N) and o2.is_contiguous(),
+                 "small_linear: outs2 are contiguous f32 [R, N]")
+    if act == 2:
+        _chk(aux is not None and aux.dtype == torch.float32 and tuple(aux.shape) == (R, N) and aux.is_contiguous(),
+             "small_linear: act 2 reads aux, contiguous f32 [R, N]")
+    dev = inp.device
+    _chk(inp.is_cuda and all(t is None or t.device == dev for ts in (Ws, outs, bs or (), outs2 or ()) for t in ts)
+         and (aux is None or aux.device == dev), "small_linear: every tensor on one GPU")
     ldw = W0.shape[1]
     for i in range(0, len(Ws), 16):
         sl = slice(i, i + 16)

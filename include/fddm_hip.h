@@ -221,7 +221,8 @@ int fddm_ln_fold(int n, const float* const* partials, const long* nslab, const l
                  float* const* dbeta, float* const* dfilm_scale, float* const* dfilm_shift,
                  const long* slabs_per_batch, void* hip_stream);
 
-/* ---- RoPE on the block input (models/denoise_decoder.py:42-53,157-159). cs/sn: [L][d]. */
+/* ---- RoPE on the block input (models/denoise_decoder.py:42-53,157-159). cs/sn: [L][d]. d must be even: both
+ *      return hipErrorInvalidValue for an odd d before any launch. */
 int fddm_rope_fwd(int out_dtype, const float* x, const float* cs, const float* sn, void* out, long N, long L, long d,
                   void* hip_stream);
 int fddm_rope_bwd(const float* dy, const float* cs, const float* sn, float* dx, long N, long L, long d,

@@ -2065,3 +2065,433 @@ def attn_fwd_case_ref(cid, kind):
     r = attn_fwd_terms64(q, k, v, x["keep"], x["drop"], p, 0.125, g, x.get("dg"), tb)
     eo, el, trip = attn_fwd_emulate(c["family"], q, k, v, x["keep"], x["drop"], p, 0.125, g, tb)
     return r, attn_fwd_units(c["family"], r, q, k, v, 0.125, "either" if c["g8"] else trip), (eo, el)
+
+
+# --------------------------------- conditioning, RoPE and embedding kernels (csrc/small.hip, csrc/misc.hip)
+# References, per-element bounds, inputs, emulations and case tables shared by tests/test_cpu_cond_ref.py (which sets
+# the constants below from the reference alone) and tests/test_gpu_cond.py (which runs the kernels).
+# fp32 evaluation in each kernel's own summation order (lin_emulate, dw_emulate, rows_mean_emulate, the oracle's
+# time_embedding, silu32 / dsilu32) against float64 in units of 2^-24 times the per-element scale, the maximum over
+# every case of the tables below, measured on the CPU: 5.19, 4.83, 3.00, 1.06, 2.31, 1.30 (tests/test_cpu_cond_ref.py
+# asserts them; the constants keep 10 % headroom). The kernels are allowed COND_C = 8 E units: the margin covers
+# contraction, the device's expf / sinf / cosf against the CPU's and the division. Hard cap 64.
+COND_E = {"lin": 5.7, "dw": 5.3, "rm": 3.3, "te": 1.2, "silu": 2.55, "g": 1.45}
+COND_C = {k: 8.0 * v for k, v in COND_E.items()}
+COND_E_FLOOR = 0.05            # stored <= 1.1 measured + this
+SILU_FLUSH = 2.0 ** -121       # expf(-v) is inf beyond -v = ln FLT_MAX = 88.72: silu32 gives 0 where |silu| < 88.73 / FLT_MAX < 2^-121
+SILU_G_ZERO = -1.2784645       # silu'(x) = 0: why act 2's second term is absolute
+
+
+class Ref:
+    """A float64 value and its per-element bound or error scale, by attribute."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _gen(*key):
+    seed = 0
+    for k in key:
+        seed = (seed * 1000003 + int(k) + 12345) % (2 ** 62)
+    return torch.Generator().manual_seed(seed)
+
+
+def _pow2(gen, n, lo=-2, hi=2):
+    return torch.pow(2.0, torch.randint(lo, hi + 1, (n,), generator=gen).float())
+
+
+def sigmoid64(x):
+    return torch.sigmoid(x.double())
+
+
+def dsilu64(x):
+    """silu'(x) = sigma (1 + x (1 - sigma))"""
+    sg = sigmoid64(x)
+    return sg * (1.0 + x.double() * (1.0 - sg))
+
+
+def silu32(v):
+    """small.hip's fp32 expression v / (1 + expf(-v))"""
+    v = v.float()
+    return v / (1.0 + torch.exp(-v))
+
+
+def dsilu32(x):
+    """small.hip's fp32 expression sg (1 + x (1 - sg)), sg = 1 / (1 + expf(-x))"""
+    x = x.float()
+    sg = 1.0 / (1.0 + torch.exp(-x))
+    return sg * (1.0 + x * (1.0 - sg))
+
+
+def silu_grid():
+    """About 4000 points over [-20, 20] with +-0, the zero of silu' +- 2^-10, and arguments at which expf overflows to
+    inf (|v| > 88.7) or its result leaves the normal range."""
+    g = torch.linspace(-20.0, 20.0, 4001, dtype=torch.float64).float()
+    extra = torch.tensor([0.0, -0.0, SILU_G_ZERO, SILU_G_ZERO - 2.0 ** -10, SILU_G_ZERO + 2.0 ** -10, -88.0, -89.0, -100.0,
+                          -1000.0, 88.0, 89.0, 100.0, 1000.0], dtype=torch.float32)
+    return torch.cat([g, extra])
+
+
+# ---- the linear family (linear4_kernel, linrt_kernel through ops.small_linear)
+LIN_MAXJ = 16                  # jobs per launch (small.hip MAXJ; ops.small_linear splits longer lists)
+# (id, kernels per launch of <= 16 jobs, R, K, N, jobs, input row strides beyond K, bias given)
+LIN_CASES = [
+    ("l4-chunk", ("linear4",), 5, 512, 40, 1, (0,), True),          # one full 512-chunk
+    ("l4-prefetch", ("linear4",), 32, 2048, 24, 1, (0,), True),     # four chunks: fetch(k0 + 512), the second stash()
+    ("l4-ragged", ("linear4",), 33, 515, 13, 1, (0,), True),        # row tile 2 holds one row; K % 4 = 3; 13 columns
+    ("l4-one", ("linear4",), 1, 1, 1, 1, (0,), True),               # the smallest shape
+    ("l4-strided", ("linear4",), 7, 100, 20, 3, (1, 4), False),     # rows off 16 bytes (scalar loads), then on; no bias
+    ("rt-trips", ("linrt",), 45, 1100, 400, 12, (0,), True),        # 18 chunks: waves 0, 1 make three trips; last 12 wide
+    ("rt-tail", ("linrt",), 45, 579, 130, 16, (0,), True),          # odd K; ragged n + 3 < N; ldw = 130 off 16 bytes
+    ("rt-short", ("linrt",), 33, 40, 130, 16, (0,), False),         # under one chunk: seven waves add zeros; no bias
+    ("l4-exact", ("linear4",), 64, 64, 64, 16, (0,), True),         # exact multiples; 64 tiles: linear4, blockIdx.z = 1
+    ("rt-exact", ("linrt",), 64, 64, 128, 16, (0,), True),          # exact multiples at 128 tiles
+    ("split", ("linrt", "linear4"), 32, 64, 256, 24, (0,), True),   # 16 jobs of 128 tiles, then 8 of 64
+    ("rt-24", ("linrt", "linrt"), 16, 96, 768, 24, (0,), True),     # both launches on linrt
+]
+
+
+def lin_dispatch(R, N, J):
+    """The kernel of every launch ops.small_linear makes for J weight sets (fddm_small_linear: linrt where the
+    32-column tiles of one launch make at least 128 blocks)."""
+    out = []
+    for j0 in range(0, J, LIN_MAXJ):
+        tiles = ((N + 31) // 32) * min(LIN_MAXJ, J - j0) * ((R + 31) // 32)
+        out.append("linrt" if tiles >= 128 else "linear4")
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def lin_operands(cid):
+    """x [R, K] = randn times a power of two per row, W [J, N, K] (the logical weights: out = x W_j^T) = randn / sqrt(K)
+    times a power of two per output column, b [J, N] = randn times the column's, aux [R, N] = 1.5 randn; powers from
+    2^-2 .. 2^2. f32 CPU tensors, never modified."""
+    _, _, R, K, N, J, _, _ = {c[0]: c for c in LIN_CASES}[cid]
+    gen = _gen(R, K, N, J)
+    rs, cs = _pow2(gen, R), _pow2(gen, N)
+    x = torch.randn(R, K, generator=gen) * rs[:, None]
+    W = torch.randn(J, N, K, generator=gen) * (cs[None, :, None] / K ** 0.5)
+    b = torch.randn(J, N, generator=gen) * cs[None, :]
+    return x, W, b, 1.5 * torch.randn(R, N, generator=gen)
+
+
+def lin_out64(y0, s0, b, aux):
+    """The three outputs of the family from y0 = sum_k x W (float64 [R, J, N]) with scale s0 = sum_k |x| |W|, the bias
+    b [J, N] or None, aux [R, N]: Ref with
+      pre, b_pre      y = y0 + b within C_lin u s, s = s0 + |b|                            (act 0's out, act 1's out)
+      silu, b_silu    silu(y) within |silu'(y)| C_lin u s + C_silu u |silu(y)| + SILU_FLUSH  (act 1's out2)
+      dx, b_dx        y0 silu'(aux) within |g| C_lin u s0 + |y0| C_g u (1 + |aux|)         (act 2: no bias)"""
+    cl = COND_C["lin"] * U24
+    y, s = y0, s0
+    if b is not None:
+        y, s = y0 + b.double()[None], s0 + b.double().abs()[None]
+    silu = y * torch.sigmoid(y)
+    a = aux.double()[:, None, :]
+    g = dsilu64(a)
+    return Ref(y0=y0, s0=s0, pre=y, s=s, b_pre=cl * s, silu=silu,
+               b_silu=dsilu64(y).abs() * cl * s + COND_C["silu"] * U24 * silu.abs() + SILU_FLUSH,
+               g=g, dx=y0 * g, b_dx=g.abs() * cl * s0 + y0.abs() * (COND_C["g"] * U24) * (1.0 + a.abs()))
+
+
+@functools.lru_cache(maxsize=None)
+def lin_ref64(cid):
+    x, W, b, aux = lin_operands(cid)
+    xd, Wd = x.double(), W.double()
+    given = {c[0]: c for c in LIN_CASES}[cid][7]
+    return lin_out64(torch.einsum("rk,jnk->rjn", xd, Wd), torch.einsum("rk,jnk->rjn", xd.abs(), Wd.abs()),
+                     b if given else None, aux)
+
+
+def lin_emulate(x, W, b, kernel):
+    """y0 and y [R, J, N] in fp32 in the kernel's order. linear4: thread quarter q owns k in [128 q, 128 q + 128) of every
+    512-chunk, one FMA chain across all chunks in k order, then ((q0 + q1) + q2) + q3 (small.hip linear4_kernel, the kk
+    loop and the `red` line). linrt: wave w owns the 64-chunks w, w + 8, ..., one FMA chain in k order, the 8 partials
+    added from 0 in wave order (linrt_kernel, the c loop and the ww loop). Then + bias."""
+    R, K = x.shape
+    J, N, _ = W.shape
+    xd, Wd = x.double(), W.double()
+    ng = 4 if kernel == "linear4" else 8
+    acc = torch.zeros(ng, R, J, N, dtype=torch.float64)       # f32 values held in float64
+    for k in range(K):
+        q = (k % 512) // 128 if kernel == "linear4" else (k // 64) % 8
+        acc[q] = (xd[:, k, None, None] * Wd[None, :, :, k] + acc[q]).float().double()
+    a = acc.float()
+    if kernel == "linear4":
+        y0 = ((a[0] + a[1]) + a[2]) + a[3]
+    else:
+        y0 = torch.zeros(R, J, N)
+        for w in range(8):
+            y0 = y0 + a[w]
+    return y0, (y0 + b.float()[None] if b is not None else y0)
+
+
+# ---- small_dw (dw_kernel)
+# one launch holds jobs of these (N, K); the last list is the 17-job call (ops.small_dw splits it 16 + 1)
+DW_SHAPES = ((40, 200), (200, 40), (33, 65), (1, 1))
+DW_DB = (True, False, True, False)                 # db given / None
+DW_ROWS = (45, 1, 64)
+DW_MANY = (17, 6, 10, 7)                           # jobs, N, K, R: equal shapes, K % 4 != 0, db on even jobs
+DW_PAD = 3                                         # dy is dybuf[:, 1 : 1 + N] of an [R, N + DW_PAD] buffer: lddy > N
+
+
+def dw_cases():
+    """(id, R, ((N, K, db given), ...))"""
+    cs = [(f"R{R}", R, tuple((n, k, g) for (n, k), g in zip(DW_SHAPES, DW_DB))) for R in DW_ROWS]
+    J, N, K, R = DW_MANY
+    return cs + [("many", R, tuple((N, K, j % 2 == 0) for j in range(J)))]
+
+
+@functools.lru_cache(maxsize=None)
+def dw_operands(cid):
+    """Per job (dybuf [R, N + DW_PAD], x [R, K], dW_old [N, K], db_old [N]): randn times a power of two per row and per
+    column of dy, per column of x (2^-2 .. 2^2); the old values carry both column scales."""
+    _, R, jobs = {c[0]: c for c in dw_cases()}[cid]
+    out = []
+    for j, (N, K, _) in enumerate(jobs):
+        gen = _gen(R, N, K, j)
+        rs, ns, ks = _pow2(gen, R), _pow2(gen, N + DW_PAD), _pow2(gen, K)
+        dyb = torch.randn(R, N + DW_PAD, generator=gen) * rs[:, None] * ns[None, :]
+        x = torch.randn(R, K, generator=gen) * ks[None, :]
+        dW = torch.randn(N, K, generator=gen) * ns[1:1 + N, None] * ks[None, :]
+        out.append((dyb, x, dW, torch.randn(N, generator=gen) * ns[1:1 + N]))
+    return out
+
+
+def dw_ref64(dy, x, dW_old, db_old):
+    """dW_new = dW_old + dy^T x with s = |dW_old| + |dy|^T |x|; db_new = db_old + sum_r dy with s = |db_old| + sum_r |dy|;
+    both within C_dw u s."""
+    dy, x, w0, b0 = dy.double(), x.double(), dW_old.double(), db_old.double()
+    c = COND_C["dw"] * U24
+    sW, sb = w0.abs() + dy.abs().t() @ x.abs(), b0.abs() + dy.abs().sum(0)
+    return Ref(dW=w0 + dy.t() @ x, sW=sW, b_dW=c * sW, db=b0 + dy.sum(0), sb=sb, b_db=c * sb)
+
+
+def dw_emulate(dy, x, dW_old, db_old):
+    """fp32 in dw_kernel's order: one FMA chain over the rows in order, then one add onto the old value; db is plain
+    adds over the rows, then one add."""
+    dyd, xd = dy.double(), x.double()
+    acc = torch.zeros(dy.shape[1], x.shape[1], dtype=torch.float64)
+    bacc = torch.zeros(dy.shape[1])
+    for r in range(dy.shape[0]):
+        acc = (dyd[r, :, None] * xd[r, None, :] + acc).float().double()
+        bacc = bacc + dy[r].float()
+    return dW_old.float() + acc.float(), db_old.float() + bacc
+
+
+# ---- rows_mean, rows_mean_masked
+RM_B = 2
+RM_S = (1, 31, 33, 128, 131, 499)
+RM_D = (8, 64, 72, 130, 512)
+RM_MASKED_EQ = (131, 499)      # all-ones mask: rows_mean's bits
+RM_HOLES_S = 131
+
+
+@functools.lru_cache(maxsize=None)
+def rm_operands(S, d, dt):
+    """x [2, S, d] = randn times a power of two per row and per column (2^-2 .. 2^2), rounded to bf16 for "bf16"."""
+    gen = _gen(S, d, dt == "bf16")
+    x = torch.randn(RM_B, S, d, generator=gen) * _pow2(gen, S)[None, :, None] * _pow2(gen, d)[None, None, :]
+    return x.to(torch.bfloat16 if dt == "bf16" else torch.float32)
+
+
+def rm_holes(S):
+    """keep [2, S] uint8: entry 0 keeps about two rows in three, never the last; entry 1 keeps nothing."""
+    keep = (torch.rand(RM_B, S, generator=_gen(S, 77)) < 0.66).to(torch.uint8)
+    keep[0, 0], keep[0, -1], keep[1] = 1, 0, 0
+    return keep
+
+
+def rm_ref64(x, keep=None):
+    """The float64 mean over the (kept) rows with s = the mean of |x| over them, within C_rm u s. Entries that keep
+    nothing: mean and s are 0 here; what the kernel writes there is asserted apart."""
+    xd = x.double()
+    if keep is None:
+        m, s = xd.mean(1), xd.abs().mean(1)
+    else:
+        k = keep.double()[..., None]
+        cnt = k.sum(1).clamp(min=1)
+        xz = torch.where(k > 0, xd, torch.zeros_like(xd))
+        m, s = xz.sum(1) / cnt, xz.abs().sum(1) / cnt
+    return Ref(mean=m, s=s, b=COND_C["rm"] * U24 * s)
+
+
+def rows_mean_emulate(x, keep=None):
+    """fp32 in the kernels' order: slice sl sums its (kept) rows sl, sl + 32, ... in order; the 32 slice sums are added
+    from 0 in order and divided by (float) the row count."""
+    B, S, d = x.shape
+    xf = x.float()
+    tot = torch.zeros(B, d)
+    for sl in range(32):
+        acc = torch.zeros(B, d)
+        for s in range(sl, S, 32):
+            row = xf[:, s]
+            acc = acc + (row if keep is None else torch.where(keep[:, s, None] > 0, row, torch.zeros_like(row)))
+        tot = tot + acc
+    n = torch.full((B, 1), float(S)) if keep is None else keep.float().sum(1, keepdim=True).clamp(min=1)
+    return tot / n
+
+
+# ---- time_embed
+TE_D = (2, 3, 4, 5, 129, 512)
+TE_T = (0, 1, 7, 200, 1000)
+TE_MAX_STEPS = 10000
+
+
+def te_ref64(t, d, max_steps=TE_MAX_STEPS, *, step_div=None, half1_bug=False, swap=False, kshift=0):
+    """[sin a, cos a, 0 if d is odd], a = t f_k, f_k = exp(-lin_k), lin_k = k ln(max_steps) / (half - 1) (0 when half
+    is 1: torch.linspace(.., steps=1) is its start), in float64, within C_te units of u (|a| (1 + lin_k) + 1): the fp32
+    roundings of lin_k and of expf reach the argument scaled by |a|, the + 1 is the sine's own. The keyword arguments
+    build the mutants of tests/test_cpu_cond_ref.py."""
+    half = d // 2
+    k = torch.arange(half, dtype=torch.float64) + kshift
+    lm = float(np.log(float(max_steps)))
+    div = (half - 1) if step_div is None else step_div
+    lin = k * (lm / div) if half > 1 else torch.full((1,), lm if half1_bug else 0.0, dtype=torch.float64)
+    a = t.double()[:, None] * torch.exp(-lin)[None, :]
+    parts = [torch.cos(a), torch.sin(a)] if swap else [torch.sin(a), torch.cos(a)]
+    unit = U24 * (a.abs() * (1.0 + lin)[None, :] + 1.0)
+    pad = [torch.zeros(t.numel(), 1, dtype=torch.float64)] * (d % 2)
+    unit = torch.cat([unit, unit] + pad, 1)
+    return Ref(emb=torch.cat(parts + pad, 1), unit=unit, b=COND_C["te"] * unit)
+
+
+# ---- RoPE (rope_fwd_kernel / rope_fwd_scalar, rope_bwd_kernel / rope_bwd_scalar); positions are r % L
+# (N, L, d, one element into a buffer)
+ROPE_CASES = [(18, 9, 128, False), (7, 7, 8, False), (12, 1, 16, False), (20, 5, 520, False),      # the vector kernels
+              (18, 9, 2, False), (7, 3, 6, False), (18, 9, 128, True)]                             # the scalar ones
+
+
+def rope_kernel_is_vector(d, off):
+    """misc.hip vec_ok: d % 8 == 0 and every tensor on a 16-byte boundary (N d < 2^31 holds in every case)."""
+    return d % 8 == 0 and not off
+
+
+@functools.lru_cache(maxsize=None)
+def rope_operands(N, L, d):
+    """x, dy, dx_old [N, d] = randn times a power of two per row and per column (2^-2 .. 2^2); cos, sin [N, d]: the
+    oracle's f32 tables for N >= L positions (the kernels read the first L rows)."""
+    from oracle import fddm_oracle as O
+    gen = _gen(N, L, d)
+    sc = _pow2(gen, N)[:, None] * _pow2(gen, d)[None, :]
+    x, dy, dx = (torch.randn(N, d, generator=gen) * sc for _ in range(3))
+    cos, sin = O.rope_cos_sin(N, O.rope_inv_freq(d))
+    return x, dy, dx, cos.contiguous(), sin.contiguous()
+
+
+def _rope_pos(N, L, pos):
+    return (torch.arange(N) % L) if pos is None else pos
+
+
+def rope_fwd_ref64(x, cos, sin, L, *, pos=None, sin_sign=1.0, halves=False):
+    """out[:, i] = x1 c - x2 s', out[:, h + i] = x1 s + x2 c' with x1 = x[:, 2i], x2 = x[:, 2i + 1], c, s the tables at
+    column 2i and c', s' at 2i + 1, within 2 u (|x1 c| + |x2 s'|): two roundings, with or without contraction. The
+    keyword arguments build the mutants (pos: positions; sin_sign; halves: pairs (i, i + h))."""
+    N, d = x.shape
+    h = d // 2
+    p = _rope_pos(N, L, pos)
+    xd, c, s = x.double(), cos.double()[p], sin.double()[p] * sin_sign
+    x1, x2 = (xd[:, :h], xd[:, h:]) if halves else (xd[:, 0::2], xd[:, 1::2])
+    t = [(x1 * c[:, 0::2], x2 * s[:, 1::2]), (x1 * s[:, 0::2], x2 * c[:, 1::2])]
+    ref = torch.cat([t[0][0] - t[0][1], t[1][0] + t[1][1]], 1)
+    return Ref(out=ref, b=2.0 * U24 * torch.cat([t[0][0].abs() + t[0][1].abs(), t[1][0].abs() + t[1][1].abs()], 1))
+
+
+def rope_bwd_ref(dy, dx_old, cos, sin, L, *, pos=None, sin_sign=1.0, halves=False):
+    """dx_new = dx_old + a C + b S at even columns, dx_old - a S + b C at odd ones (a = dy[:, i], b = dy[:, h + i];
+    rope_bwd_ref64 above), within 3 u (|dx_old| + |a C| + |b S|): three roundings."""
+    N, d = dy.shape
+    p = _rope_pos(N, L, pos)
+    c, s = cos.double()[p], sin.double()[p] * sin_sign      # gathered per row: rope_bwd_ref64 below takes them with L = N
+    if halves:
+        h = d // 2
+        a, b = dy.double()[:, :h], dy.double()[:, h:]
+        t = torch.cat([a * c[:, 0::2] + b * s[:, 0::2], -a * s[:, 1::2] + b * c[:, 1::2]], 1)
+        m = torch.cat([(a * c[:, 0::2]).abs() + (b * s[:, 0::2]).abs(), (a * s[:, 1::2]).abs() + (b * c[:, 1::2]).abs()], 1)
+    else:
+        t = rope_bwd_ref64(dy.double(), c, s, N)
+        m = rope_bwd_ref64(dy.double().abs(), c.abs(), s.abs(), N, magnitude=True)
+    return Ref(dx=dx_old.double() + t, b=3.0 * U24 * (dx_old.double().abs() + m))
+
+
+def rope_fwd_eval32(x, cos, sin, L, order):
+    """The forward in fp32: order 0 rounds the second product and feeds the first through an FMA, order 1 the other
+    way round, order 2 rounds both products (no contraction)."""
+    N, d = x.shape
+    p = torch.arange(N) % L
+    c, s = cos[p], sin[p]
+    x1, x2 = x[:, 0::2], x[:, 1::2]
+
+    def comb(u, cu, v, cv):
+        if order == 0:
+            return _fma32(u, cu, v * cv)
+        if order == 1:
+            return _fma32(v, cv, u * cu)
+        return u * cu + v * cv
+    return torch.cat([comb(x1, c[:, 0::2], -x2, s[:, 1::2]), comb(x1, s[:, 0::2], x2, c[:, 1::2])], 1)
+
+
+def rope_bwd_eval32(dy, dx_old, cos, sin, L, order):
+    """The backward in fp32: t = a C + b S as in rope_fwd_eval32 (orders 0 - 2), then dx_old + t; order 3 is two chained
+    FMAs onto dx_old."""
+    N, d = dy.shape
+    h = d // 2
+    p = torch.arange(N) % L
+    c, s = cos[p], sin[p]
+    a, b = dy[:, :h], dy[:, h:]
+
+    def comb(u, cu, v, cv, old):
+        if order == 0:
+            return old + _fma32(u, cu, v * cv)
+        if order == 1:
+            return old + _fma32(v, cv, u * cu)
+        if order == 2:
+            return old + (u * cu + v * cv)
+        return _fma32(u, cu, _fma32(v, cv, old))
+    out = torch.empty_like(dx_old)
+    out[:, 0::2] = comb(a, c[:, 0::2], b, s[:, 0::2], dx_old[:, 0::2])
+    out[:, 1::2] = comb(-a, s[:, 1::2], b, c[:, 1::2], dx_old[:, 1::2])
+    return out
+
+
+# ---- token embedding (embed_fwd_kernel / embed_fwd_scalar, embed_bwd_kernel)
+# (d, L, B, V, pad_id): B L is no multiple of 8; rows 8 .. 15 (one whole block of embed_bwd) are padding
+EMBED_CASES = [(8, 1, 21, 5, 0), (520, 3, 7, 50, 3), (6, 9, 3, 5, 3), (520, 9, 3, 5, 0), (8, 3, 7, 50, 0), (6, 1, 21, 50, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def embed_operands(d, L, B, V, pad_id):
+    """tok [B L] int64 in [0, V) with rows 8 .. 15 and one more set to pad_id; E, dE_old [V, d], tbias, dtb_old [B, d],
+    dx [B L, d]: randn times powers of two per row and column (2^-2 .. 2^2)."""
+    gen = _gen(d, L, B, V, pad_id)
+    N = B * L
+    tok = torch.randint(0, V, (N,), generator=gen)
+    tok[8:16] = pad_id
+    tok[N - 2] = pad_id
+    cs = _pow2(gen, d)[None, :]
+    E, dE = (torch.randn(V, d, generator=gen) * _pow2(gen, V)[:, None] * cs for _ in range(2))
+    tb, dtb = (torch.randn(B, d, generator=gen) * _pow2(gen, B)[:, None] * cs for _ in range(2))
+    return tok, E, tb, torch.randn(N, d, generator=gen) * _pow2(gen, N)[:, None] * cs, dE, dtb
+
+
+def embed_fwd_exact(tok, E, tbias, L):
+    """E[tok] + tbias[r // L] in fp32 by torch: one IEEE add per element, so the kernel's bits."""
+    x = E[tok]
+    return x if tbias is None else x + tbias[torch.arange(tok.numel()) // L]
+
+
+def embed_bwd_ref64(tok, dx, dE_old, dtb_old, L, pad_id, *, count_pad=False, dtb_shift=0):
+    """dE_new[v] = dE_old[v] + the sum of dx over the rows naming v (none for pad_id), within n u (|old| + sum |dx|),
+    n the number of such rows (n = 0: the old bits); dtb_new[b] = dtb_old[b] + sum_l dx[b, l] within (L + 1) u (..):
+    L - k adds inside the blocks and k atomics for an entry spread over k blocks. The keyword arguments build the
+    mutants."""
+    V, d = dE_old.shape
+    B = dtb_old.shape[0]
+    dxd = dx.double()
+    live = torch.ones_like(tok, dtype=torch.bool) if count_pad else tok != pad_id
+    add = torch.zeros(V, d, dtype=torch.float64).index_add_(0, tok[live], dxd[live])
+    mag = torch.zeros(V, d, dtype=torch.float64).index_add_(0, tok[live], dxd[live].abs())
+    n = torch.zeros(V, dtype=torch.float64).index_add_(0, tok[live], torch.ones(int(live.sum()), dtype=torch.float64))
+    tb = dxd.view(B, L, d).sum(1).roll(-dtb_shift, 0)
+    tbm = dxd.abs().view(B, L, d).sum(1).roll(-dtb_shift, 0)
+    return Ref(dE=dE_old.double() + add, b_dE=n[:, None] * U24 * (dE_old.double().abs() + mag), n=n,
+               dtb=dtb_old.double() + tb, b_dtb=(L + 1) * U24 * (dtb_old.double().abs() + tbm))
