@@ -10,7 +10,13 @@
 //
 // Non-greedy decoding (posterior_mode "average", greedy=False) draws from the same posterior,
 // tempered as the reference does (softmax(log(clamp(p, 1e-12)) / temperature)), by a Gumbel-max race
-// on the build's counter RNG (mix64(seed, stream, row·V + k)).
+// on the build's counter RNG: class k of row `row` draws h = mix64(seed, stream, row·V + k) and
+// u = ((h >> 41) + 0.5) · 2^-23. The 23 bits plus the half are exact in fp32, so 2^-24 <= u <= 1 - 2^-24 for every h
+// and the Gumbel term -log(-log u) is finite (24 bits would round the top draw to u = 1 and the term to +inf).
+//
+// Every id written lies in [0, V): x_t is clamped on the way in, and a row with no orderable entry (all NaN, all
+// -inf), on which no comparison of the searches below is ever true, gets torch.argmax's answer for an all -inf row:
+// 0, and the first k ≠ x_t.
 #include "common.h"
 
 namespace fddm {
@@ -70,6 +76,9 @@ __global__ __launch_bounds__(256) void jump_kernel(JumpArgs a) {
     better(m, mi, __shfl_xor(m, s, 64), __shfl_xor(mi, s, 64));
     better(o, oi, __shfl_xor(o, s, 64), __shfl_xor(oi, s, 64));
   }
+  // nothing orderable (every entry, or every entry but x_t's, NaN or -inf): the first index, as torch.argmax
+  if (mi >= V) mi = 0;
+  if (oi >= V) oi = (x == 0) ? 1 : 0;
   // pass 2: softmax normaliser
   float sum = 0.f;
   if (vec) {
@@ -113,14 +122,14 @@ __global__ __launch_bounds__(256) void jump_kernel(JumpArgs a) {
       if (a.mode & JUMP_FAST) P = (float)abar * xh + (1.f - (float)abar) / (float)V;
       else P = (float)(((k == x ? ac : 0.0) + bc) * (atg * xh + btg) / Zn);
       const uint64_t h = mix64(a.seed, a.stream, (uint64_t)row * (uint64_t)V + (uint64_t)k);
-      const float u = ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
+      const float u = ((float)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);  // exact in fp32: 0 < u < 1
       const float g = -__logf(-__logf(u));
       const float sc = __logf(fmaxf(P, 1e-12f)) * a.inv_temp + g;
       if (sc > best) { best = sc; bi = k; }
     }
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) better(best, bi, __shfl_xor(best, s, 64), __shfl_xor(bi, s, 64));
-    nx = bi;
+    nx = bi < V ? bi : mi;  // every score NaN (a row without an orderable entry): no class ever led the race
   }
   if (lane == 0) {
     a.xnext[row] = nx;

@@ -36,6 +36,16 @@ def mix64(seed: int, stream: int, idx: np.ndarray) -> np.ndarray:
     return z
 
 
+def jump_uniform(h: np.ndarray, dtype=np.float64) -> np.ndarray:
+    """The uniform draw of the jumpy sampler's Categorical (csrc/jumpy.hip, JUMP_SAMPLE): class k of row r draws
+    h = mix64(seed, stream, r*V + k) and u = ((h >> 41) + 0.5) * 2^-23. 23 bits plus the half fit fp32's 24-bit
+    significand, so the fp32 value is the exact one and 2^-24 <= u <= 1 - 2^-24 for every h: the Gumbel term
+    -log(-log u) is finite. (Contract v1 took 24 bits, (h >> 40) + 0.5 over 2^24: 16777215.5 is no fp32 value and ties
+    to 2^24, u = 1 and a Gumbel term of +inf once in 2^24 draws.) `dtype` evaluates the same expression in that type."""
+    j = (np.asarray(h, dtype=np.uint64) >> np.uint64(41)).astype(dtype)
+    return (j + dtype(0.5)) * dtype(2.0 ** -23)
+
+
 def dropout_keep(seed: int, stream: int, numel: int, p: float) -> torch.Tensor:
     """Keep-mask for `numel` elements: element e keeps iff u16(e) >= round(p*65536), where
     u16(e) = bits [16*(e&3), 16*(e&3)+16) of mix64(seed, stream, e>>2)."""

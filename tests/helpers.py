@@ -2495,3 +2495,370 @@ def embed_bwd_ref64(tok, dx, dE_old, dtb_old, L, pad_id, *, count_pad=False, dtb
     tbm = dxd.abs().view(B, L, d).sum(1).roll(-dtb_shift, 0)
     return Ref(dE=dE_old.double() + add, b_dE=n[:, None] * U24 * (dE_old.double().abs() + mag), n=n,
                dtb=dtb_old.double() + tb, b_dtb=(L + 1) * U24 * (dtb_old.double().abs() + tbm))
+
+
+# --------------------------------- the jumpy-sampler step (csrc/jumpy.hip: jump_kernel, ops.jump)
+# The float64 reference of one jump, an fp32 emulation in the kernel's own evaluation order, the per-row bounds and
+# the case table, shared by tests/test_cpu_jump_ref.py (which sets the constants from the reference and the
+# emulation alone) and tests/test_gpu_jump.py (which runs the kernel).
+#
+# What the kernel rounds. The row max m and both argmax searches compare fp32 values: exact. The softmax normaliser
+# s = sum_k expf(z_k - m) is an fp32 sum of fp32 terms, each with the rounding of z_k - m (which moves the term by
+# u |d_k|, d_k = z_k - m) and of expf; 1 / s, x^_{x_t}, x^_o and both greedy scores are double. So a greedy decision
+# carries one error, the relative error delta of s, common to p_x and p_o:
+#     |margin - margin64| <= delta W,   W = ((a_cum + b_cum) a_tg p_x + b_cum a_tg p_o) / max(s_x, s_o)
+#     delta <= (C_g + K_exp) u S,       S = sum_k e_k (1 + |d_k|) / sum_k e_k   (the absolute-value evaluation of s)
+# A sampled score log(max(P_k, 1e-12)) / temp + g_k adds fp32 x^_k = expf(d_k) (float)(1 / s), P_k (delta once more
+# through the normaliser Z of the exact posterior), logf, the product with 1 / temp, the Gumbel term and the last add:
+#     |score_k - score64_k| <= (C_s + K_dev) u U_k
+#     U_k = (2 S + (1 + |d_k|) + (1 + |lp_k|) + |lp_k|) / temp + (1 + |g_k|) + |score_k|,   lp_k = log max(P_k, 1e-12)
+# E: the emulation's largest excess over every case in those units, measured on the CPU (numpy's correctly rounded
+# fp32 exp / log): greedy 1.014, sample 0.711 (tests/test_cpu_jump_ref.py asserts measured <= stored <= 1.1 measured +
+# 0.05). C = 8 E, hard cap 64. The device's __expf / __logf are not numpy's: their error has its own term K, from one
+# grid on an MI355X against float64 (not from jump_kernel), in the units above:
+#     __expf on [-87, 0], 2^22 points:                |err| / (u (1 + |x|) exp x)     <= JUMP_K["exp"]
+#     __logf on [1e-12, 1], 2^22 + 2^16 points:       |err| / (u (1 + |log x|))       <= JUMP_K["log"]
+#     -__logf(-__logf(u)) for all 2^23 draws u:       |err| / (u (1 + |g|))           <= JUMP_K["gum"]
+# Below -87.3 expf's result is denormal and the device writes 0: an absolute 2^-126 per term, V 2^-126 relative to s >= 1.
+JUMP_FAST, JUMP_SAMPLE = 1, 2
+JUMP_E = {"greedy": 1.1, "sample": 0.75}
+JUMP_E_FLOOR = 0.05
+JUMP_C = {k: min(64.0, 8.0 * v) for k, v in JUMP_E.items()}
+JUMP_K = {"exp": 1.5, "log": 3.5, "gum": 3.3}      # measured 1.204, 2.966, 2.977 (the last over every draw)
+JUMP_K_DEV = max(JUMP_K.values())
+JUMP_V = (2, 3, 63, 64, 65, 255, 256, 257, 260, 2003)
+JUMP_SAMPLE_V = JUMP_V[:-1]                          # the draw is checked up to V = 260
+JUMP_LAYOUTS = ("contig", "pad4", "pad1", "off1")    # ldz = V, V + 4, V + 1; the base one float past 16 bytes
+JUMP_NL = tuple((N, L) for N in (1, 5, 64) for L in (1, 5, 16))
+JUMP_SAMPLE_NL = ((64, 5), (64, 16), (5, 1), (1, 16))
+JUMP_TEMPS = (0.7, 1.0, 2.0)
+JUMP_T, JUMP_BETA_MAX, JUMP_DELTA = 200, 0.2, 5
+JUMP_PAD = 1e30                                      # padding columns: an over-read changes the argmax
+JUMP_SENTINEL = -0x5A5A5A5A5A5A5A5B                  # output buffers around the slice the kernel writes
+JUMP_KINDS = ("rand", "tie4", "ninf", "bis+", "bis-", "tie64", "tie256", "tie2", "ru4", "ru64", "ru256", "ru2",
+              "const", "rand", "ninf_x", "peaked")
+JUMP_PEAK = 40.0                                     # logit spread of the peaked rows: most P on the 1e-12 clamp
+JUMP_BISECT_AT = 4.0                                 # constructed rows sit at margin = +-4 bounds
+# seeds whose draw of (row, class) is extreme for N = 64, V = 256, stream 7: every bit of h >> 41 set (and of h >> 40,
+# contract v1's 24 bits), resp. clear (found by a CPU search; tests/test_cpu_jump_ref.py re-derives them)
+JUMP_ONES = ((2678, 5, 144), (3227, 49, 149), (3651, 41, 176))
+JUMP_ZERO = (200, 28, 109)
+JUMP_STREAM = 7
+
+
+def jump_is_vector(V, layout):
+    """jump_kernel's float4 path: V and ldz multiples of 4 and a 16-byte aligned base."""
+    return V % 4 == 0 and layout in ("contig", "pad4")
+
+
+def jump_ldz(V, layout):
+    return V + {"contig": 0, "pad4": 4, "pad1": 1, "off1": 0}[layout]
+
+
+def _jump_rows(logits, xt, coef, L):
+    z = np.asarray(logits, dtype=np.float64)
+    N, V = z.shape
+    x = np.clip(np.asarray(xt, dtype=np.int64), 0, V - 1)
+    cf = np.asarray(coef, dtype=np.float32).reshape(-1, 4).astype(np.float64)[np.arange(N) // L]
+    return z, N, V, x, cf
+
+
+def jump_ref64(logits, xt, coef, L, mode=0, temperature=1.0, seed=0, stream=0):
+    """One jump in float64, per row: `am` the first argmax (0 for a row without an orderable entry, NaN counting as
+    -inf: torch.argmax's answer for an all -inf row), `o` the first argmax over k != x_t (x_t clamped into [0, V)),
+    `sx`, `so` and `margin` = (sx - so) / max(sx, so), `choice` the greedy x_{t-delta} (fast mode: am), `munit` = S W,
+    the margin's error scale (the comment above), `ok` False for a row without an orderable entry; with JUMP_SAMPLE
+    also `score` [N, V] = log(max(P_k, 1e-12)) / temp + g_k with P from the float64 softmax and g from the contract's
+    u in float64 (oracle.jump_uniform), `P`, `g`, and `unit` = U_k."""
+    from oracle import fddm_oracle as O
+    z, N, V, x, cf = _jump_rows(logits, xt, coef, L)
+    r = np.arange(N)
+    zc = np.where(np.isnan(z), -np.inf, z)
+    m = zc.max(1)
+    ok = np.isfinite(m)
+    am = zc.argmax(1)
+    zo = zc.copy()
+    zo[r, x] = -np.inf
+    o = np.where(np.isfinite(zo.max(1)), zo.argmax(1), np.where(x == 0, 1, 0))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        d = zc - m[:, None]
+        e = np.exp(d)
+        s = e.sum(1)
+        xh = e / s[:, None]
+        ad = np.where(e > 0, np.abs(d), 0.0)
+        S = (e * (1.0 + ad)).sum(1) / s
+        ac, bc, atg, btg = cf.T
+        px, po = xh[r, x], xh[r, o]
+        sx = (ac + bc) * (atg * px + btg)
+        so = bc * (atg * po + btg)
+        top = np.maximum(np.maximum(sx, so), 1e-300)
+        margin = (sx - so) / top
+        W = ((ac + bc) * atg * px + bc * atg * po) / top
+    choice = am if mode & JUMP_FAST else np.where((sx > so) | ((sx == so) & (x < o)), x, o)
+    out = Ref(am=am, o=o, x=x, sx=sx, so=so, margin=margin, choice=choice, S=S, munit=S * W, ok=ok, xh=xh)
+    if mode & JUMP_SAMPLE:
+        temp = float(np.float32(temperature))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            if mode & JUMP_FAST:
+                P = ac[:, None] * xh + (1.0 - ac[:, None]) / V
+            else:
+                A = np.broadcast_to(bc[:, None], (N, V)).copy()
+                A[r, x] += ac
+                un = A * (atg[:, None] * xh + btg[:, None])
+                P = un / un.sum(1, keepdims=True)
+            lp = np.log(np.maximum(P, 1e-12))
+            h = O.mix64(seed, stream, r[:, None].astype(np.uint64) * np.uint64(V) + np.arange(V, dtype=np.uint64)[None])
+            g = -np.log(-np.log(O.jump_uniform(h)))
+            score = lp / temp + g
+            unit = (2.0 * S[:, None] + (1.0 + ad) + (1.0 + np.abs(lp)) + np.abs(lp)) / temp + (1.0 + np.abs(g)) + \
+                np.abs(score)
+        out.__dict__.update(P=P, g=g, score=score, unit=unit, lp=lp)
+    return out
+
+
+def jump_greedy_bound(ref, V, C=None):
+    """Per row: how far the kernel's margin may lie from ref.margin."""
+    C = JUMP_C["greedy"] if C is None else C
+    return (C + JUMP_K["exp"]) * U24 * ref.munit + V * 2.0 ** -126 + 2.0 ** -48
+
+
+def jump_sample_bound(ref, C=None):
+    """Per row: a class whose float64 score lies further than this under the row's best cannot win on the kernel
+    (twice the largest per-class score error)."""
+    C = JUMP_C["sample"] if C is None else C
+    return 2.0 * ((C + JUMP_K_DEV) * U24 * ref.unit).max(1)
+
+
+def jump_candidates(ref):
+    """[N, V] bool: the classes the kernel may draw."""
+    return ref.score >= (ref.score.max(1) - jump_sample_bound(ref))[:, None]
+
+
+def jump_emulate(logits, xt, coef, L, mode=0, temperature=1.0, seed=0, stream=0, vector=False):
+    """The kernel's own evaluation in numpy: fp32 expf terms summed per lane in the kernel's order (float4 path: lane l
+    takes k = 4 l + 256 p .. + 3, `sum += ((e0 + e1) + e2) + e3`; scalar path: k = l + 64 p), the xor tree of wave_sum,
+    then the double-precision tail for p_x, p_o, s_x, s_o; with JUMP_SAMPLE the fp32 x^, P, logf and Gumbel term.
+    Returns (margin [N], score [N, V] or None). Rows need an orderable entry."""
+    from oracle import fddm_oracle as O
+    f = np.float32
+    z64, N, V, x, cf = _jump_rows(logits, xt, coef, L)
+    z = np.asarray(logits, dtype=f)
+    r = np.arange(N)
+    m = z.max(1)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        e = np.exp((z - m[:, None]).astype(f)).astype(f)
+        span = 256 if vector else 64
+        Wd = -(-V // span) * span
+        ep = np.zeros((N, Wd), dtype=f)
+        ep[:, :V] = e
+        lanes = np.zeros((N, 64), dtype=f)
+        if vector:
+            q = ep.reshape(N, Wd // 256, 64, 4)
+            for p in range(Wd // 256):
+                lanes = lanes + (((q[:, p, :, 0] + q[:, p, :, 1]) + q[:, p, :, 2]) + q[:, p, :, 3])
+        else:
+            q = ep.reshape(N, Wd // 64, 64)
+            for p in range(Wd // 64):
+                lanes = lanes + q[:, p]
+        idx = np.arange(64)
+        for sft in (32, 16, 8, 4, 2, 1):
+            lanes = lanes + lanes[:, idx ^ sft]
+        assert lanes.dtype == f
+        s = lanes[:, 0]
+        inv_s = 1.0 / s.astype(np.float64)
+        zo = z64.copy()
+        zo[r, x] = -np.inf
+        oval = zo.max(1)
+        ac, bc, atg, btg = cf.T
+        px = np.exp(z64[r, x] - m.astype(np.float64)) * inv_s
+        po = np.exp(oval - m.astype(np.float64)) * inv_s
+        sx = (ac + bc) * (atg * px + btg)
+        so = bc * (atg * po + btg)
+        margin = (sx - so) / np.maximum(np.maximum(sx, so), 1e-300)
+        if not mode & JUMP_SAMPLE:
+            return margin, None
+        inv_sf = inv_s.astype(f)
+        xh = e * inv_sf[:, None]
+        assert xh.dtype == f
+        if mode & JUMP_FAST:
+            ab = ac.astype(f)[:, None]
+            P = ab * xh + ((f(1.0) - ab) / f(V))
+        else:
+            Zn = bc * (atg + V * btg) + ac * (atg * px + btg)
+            A = np.broadcast_to(bc[:, None], (N, V)).copy()
+            A[r, x] += ac
+            P = (A * (atg[:, None] * xh.astype(np.float64) + btg[:, None]) / Zn[:, None]).astype(f)
+        assert P.dtype == f
+        h = O.mix64(seed, stream, r[:, None].astype(np.uint64) * np.uint64(V) + np.arange(V, dtype=np.uint64)[None])
+        u = O.jump_uniform(h, f)
+        g = -np.log(-np.log(u))
+        inv_temp = f(1.0) / f(temperature)
+        score = np.log(np.maximum(P, f(1e-12))) * inv_temp + g
+        assert u.dtype == f and g.dtype == f and score.dtype == f
+    return margin, score
+
+
+def jump_coefs(V, B, fast):
+    """[B, 4] f32 step coefficients, different per batch element: exact {a_cum, b_cum, a_tg, b_tg} of a jump of
+    JUMP_DELTA from t_b (oracle.jump_coeffs), fast {abar_{t_b - delta}, 0, 0, 0}. Element B // 2 has t - delta = 0:
+    a_tg = 1, b_tg = 0, abar = 1."""
+    from oracle import fddm_oracle as O
+    betas, abar = (np.asarray(v, dtype=np.float32) for v in O.sched_tables(JUMP_T, JUMP_BETA_MAX))
+    ts = [JUMP_DELTA + (53 * b + 17) % (JUMP_T - JUMP_DELTA + 1) for b in range(B)]
+    ts[B // 2] = JUMP_DELTA
+    c = np.zeros((B, 4), dtype=np.float32)
+    for b, t in enumerate(ts):
+        if fast:
+            c[b, 0] = abar[t - JUMP_DELTA - 1] if t > JUMP_DELTA else 1.0
+        else:
+            c[b] = O.jump_coeffs(betas, V, JUMP_T, t, JUMP_DELTA)
+    return c
+
+
+def _jump_pair(kind, V, gen):
+    """Two classes that share a float4 ("4"), a lane on consecutive passes of the scalar ("64") or the float4 path
+    ("256"), or neither ("2"); the nearest placement that fits V otherwise."""
+    ri = lambda n: int(torch.randint(0, max(1, n), (1,), generator=gen))
+    if kind == "4":
+        if V >= 4:
+            k = 4 * ri((V - 3) // 4 + 1) + 1
+            return k, k + 1
+        return V - 2, V - 1
+    if kind == "256" and V > 256:
+        k = ri(V - 256)
+        return k, k + 256
+    if kind in ("64", "256") and V > 64:
+        k = ri(V - 64)
+        return k, k + 64
+    if V > 9:
+        k = ri(V - 9)
+        return k, k + 9
+    return 0, V - 1
+
+
+@functools.lru_cache(maxsize=None)
+def jump_case(V, N, L):
+    """Inputs of case (V, N, L), the same for every layout: `logits` [N, V] f32, `xt` [N] (0, V - 1, the argmax, a
+    non-argmax, -1, V + 5 in turn), `coef` / `coef_fast` [B, 4], `kinds` per row (JUMP_KINDS, rotated per case so that N
+    = 1 and 5 meet different ones) and `built` [N]: +-1 on the rows whose logit at x_t was bisected until the exact
+    greedy margin sits at +-JUMP_BISECT_AT bounds, 0 elsewhere (a "bis" row on which no logit reaches that margin stays
+    an ordinary row)."""
+    gen = _gen(7001, V, N, L)
+    B = (N + L - 1) // L
+    coef, coef_fast = jump_coefs(V, B, False), jump_coefs(V, B, True)
+    z = (3.0 * torch.randn(N, V, generator=gen)).numpy().astype(np.float32)
+    rot = (V + 3 * N + 5 * L) % 16
+    kinds = [JUMP_KINDS[(r + rot) % 16] for r in range(N)]
+    xt = np.zeros(N, dtype=np.int64)
+    for r, kind in enumerate(kinds):
+        top = float(np.abs(z[r]).max())
+        if kind == "peaked":
+            z[r] = (JUMP_PEAK * torch.rand(V, generator=gen) ** 3).numpy()       # two thirds more than 27.6 under the top
+            z[r, int(torch.randint(0, V, (1,), generator=gen))] = JUMP_PEAK
+            z[r, int(torch.randint(0, V, (1,), generator=gen))] = 0.0
+        elif kind == "const":
+            z[r] = z[r, 0]
+        elif kind.startswith("tie"):
+            k1, k2 = _jump_pair(kind[3:], V, gen)
+            z[r, k1] = z[r, k2] = top + 1.5
+        elif kind.startswith("ru") and V > 2:
+            k1, k2 = _jump_pair(kind[2:], V, gen)
+            p = (k2 + 3) % V
+            while p in (k1, k2):
+                p = (p + 1) % V
+            z[r, k1] = z[r, k2] = top + 1.5
+            z[r, p] = top + 3.0
+        am = int(z[r].argmax())
+        xk = (r + rot // 2) % 6
+        xt[r] = (0, V - 1, am, (am + 1 + int(torch.randint(0, V - 1, (1,), generator=gen))) % V, -1, V + 5)[xk]
+        if kind.startswith("ru") and V > 2:
+            xt[r] = am
+        x = min(max(int(xt[r]), 0), V - 1)
+        if kind in ("ninf", "ninf_x"):
+            hole = (torch.rand(V, generator=gen) < 0.3).numpy()
+            keep = (x + 1 + r % (V - 1)) % V            # a finite class other than x_t
+            hole[keep] = False
+            hole[x] = kind == "ninf_x"
+            z[r, hole] = -np.inf
+    built = np.zeros(N, dtype=np.int64)
+    for r, kind in enumerate(kinds):
+        if kind in ("bis+", "bis-"):
+            built[r] = _jump_bisect_row(z, xt, coef, L, r, 1 if kind == "bis+" else -1)
+    for a in (z, xt, coef, coef_fast, built):
+        a.setflags(write=False)
+    return dict(logits=z, xt=xt, coef=coef, coef_fast=coef_fast, kinds=kinds, built=built, V=V, N=N, L=L)
+
+
+def _jump_bisect_row(z, xt, coef, L, r, sign):
+    """Move z[r, x_t] until the row's exact greedy margin is sign * JUMP_BISECT_AT bounds; the best other class gets
+    most of the mass first, so that the margin changes sign over the range. Returns sign, or 0 with the row restored."""
+    V = z.shape[1]
+    x = min(max(int(xt[r]), 0), V - 1)
+    saved = z[r].copy()
+    o = (x + 1 + r % (V - 1)) % V
+    z[r, o] = np.abs(saved).max() + 4.0
+    lo, hi = float(z[r, o]) - 40.0, 48.0
+    cf = coef[r // L][None]
+
+    def ref_at(v):
+        row = z[r:r + 1].copy()
+        row[0, x] = np.float32(lo + v)
+        return jump_ref64(row, [x], cf, 1)
+
+    def f(v, k):
+        q = ref_at(v)
+        return float(q.margin[0] - sign * k * jump_greedy_bound(q, V)[0])
+
+    if not (f(0.0, JUMP_BISECT_AT) < 0.0 < f(hi, JUMP_BISECT_AT)):
+        z[r] = saved
+        return 0
+    v = _bisect(lambda t: f(t, JUMP_BISECT_AT), hi, target=0.0, steps=60)
+    z[r, x] = np.float32(lo + v)
+    q = jump_ref64(z[r:r + 1], [x], cf, 1)
+    k = float(q.margin[0] / jump_greedy_bound(q, V)[0]) * sign
+    if not JUMP_BISECT_AT - 1.0 <= k <= JUMP_BISECT_AT + 1.0:      # fp32 steps of the logit too coarse for this row
+        z[r] = saved
+        return 0
+    return sign
+
+
+@functools.lru_cache(maxsize=None)
+def jump_case_ref(V, N, L, mode, temperature=1.0):
+    """(reference, seed) of case (V, N, L) under `mode`, computed once."""
+    c = jump_case(V, N, L)
+    seed = 1000 + 7 * V + 3 * N + L
+    return jump_ref64(c["logits"], c["xt"], c["coef_fast"] if mode & JUMP_FAST else c["coef"], L, mode, temperature,
+                      seed, JUMP_STREAM), seed
+
+
+def jump_extreme_case(which):
+    """N = 64, V = 256 rows whose draw of one (row, class) is extreme. which = 0, 1, 2: the JUMP_ONES seeds, every bit of
+    the draw set; that class gets a probability under the 1e-12 clamp and class 3 nearly all the mass, so the reference
+    picks class 3 by a wide margin (u = 1 and a Gumbel term of +inf pick the clamped class instead). which = "zero": the
+    draw with every bit clear (JUMP_ZERO); its class gets nearly all the mass and still loses only if its Gumbel term is
+    far below -log(-log 2^-24) = -2.81."""
+    seed, row, k = JUMP_ONES[which] if which != "zero" else JUMP_ZERO
+    N, V, L = 64, 256, 64          # one batch element, t - delta = 0: b_tg = 0 and abar = 1, so P can reach the clamp
+    z = (1.0 * torch.randn(N, V, generator=_gen(7002, seed))).numpy().astype(np.float32)
+    if which == "zero":
+        z[row, k] = 14.0
+    else:
+        z[row, k] = -36.0
+        z[row, 3] = 14.0
+    xt = np.full(N, k if which == "zero" else 3, dtype=np.int64)      # x_t on the favoured class: a_cum is on its side
+    return dict(logits=z, xt=xt, coef=jump_coefs(V, N // L, False), coef_fast=jump_coefs(V, N // L, True), V=V, N=N,
+                L=L, seed=seed, row=row, k=k)
+
+
+@functools.lru_cache(maxsize=None)
+def jump_peaked_case():
+    """N = 64, V = 260, every row with a logit spread of JUMP_PEAK and one batch element with t - delta = 0 (b_tg = 0, abar
+    = 1: nothing but x^ keeps P off the floor), so that most P sit on the 1e-12 clamp."""
+    N, V, L = 64, 260, 64
+    gen = _gen(7004)
+    z = (JUMP_PEAK * torch.rand(N, V, generator=gen) ** 3).numpy().astype(np.float32)
+    r = np.arange(N)
+    z[r, (7 * r) % V] = JUMP_PEAK
+    z[r, (7 * r + 1) % V] = 0.0
+    xt = torch.randint(0, V, (N,), generator=gen).numpy()
+    return dict(logits=z, xt=xt, coef=jump_coefs(V, 1, False), coef_fast=jump_coefs(V, 1, True), V=V, N=N, L=L, seed=4242)

@@ -72,12 +72,14 @@ def test_jumpy_sampler_matches_reference_run(mode, graph, monkeypatch):
         np.testing.assert_allclose(p.max(-1).values.cpu().numpy(), g[f"run_{mode}_plast_max"], rtol=1e-4)
 
 
-@pytest.mark.parametrize("mode,temp", [("exact", 1.0), ("exact", 0.7), ("fast", 1.0)])
-def test_jump_categorical_draw_matches_posterior(mode, temp):
+@pytest.mark.parametrize("mode,temp,V", [pytest.param("exact", 1.0, 16, id="exact-1.0"), pytest.param("exact", 0.7, 16, id="exact-0.7"),
+                                         pytest.param("fast", 1.0, 16, id="fast-1.0"), pytest.param("exact", 1.0, 200, id="exact-1.0-V200")])
+def test_jump_categorical_draw_matches_posterior(mode, temp, V):
     """greedy=False: draws over many identical rows follow the tempered posterior the reference's
-    Categorical samples (jumpy_sampler.py:153-162): per-class frequencies within 5 sigma."""
+    Categorical samples (jumpy_sampler.py:153-162): per-class frequencies within 5 sigma. V = 200: every lane's draw loop
+    takes more than one pass."""
     from fddm_hip import ops
-    V, N, L = 16, 200000, 1000
+    N, L = 200000, 1000
     gen = torch.Generator().manual_seed(11)
     row = torch.randn(V, generator=gen) * 1.5
     xt_val = 3
