@@ -664,14 +664,16 @@ FDDM_API int fddm_ln_fwd(int x_dtype, int y_dtype, int out_dtype, const void* x,
                          void* out_t, float* save_s, float* mean, float* rstd, long N, long d, long rows_per_batch,
                          float eps, float drop_p, unsigned long long seed, unsigned long long stream,
                          const float* rope_cos, const float* rope_sin, void* rope_out, long rope_L, void* hs) {
+  if (d <= 0) return (int)hipErrorInvalidValue;
   if (N <= 0) return 0;
   if (d > 64 * 8 * LN_MAXCH || d % 8) return (int)hipErrorInvalidValue;
   if (rope_out && (!rope_cos || !rope_sin || rope_L <= 0 || d % 16 ||
                    (((uintptr_t)rope_cos | (uintptr_t)rope_sin | (uintptr_t)rope_out) & 15)))
     return (int)hipErrorInvalidValue;
   if ((((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)film_scale | (uintptr_t)film_shift | (uintptr_t)x |
-        (uintptr_t)y) & 15))
-    return (int)hipErrorInvalidValue;  // 16-B vector accesses
+        (uintptr_t)y | (uintptr_t)out_f32 | (uintptr_t)out_t | (uintptr_t)save_s) & 15) ||
+      (((uintptr_t)mean | (uintptr_t)rstd) & 3))
+    return (int)hipErrorInvalidValue;  // 16-B vector accesses (mean, rstd: one float per row)
   LnFwdArgs a{x, y, gamma, beta, film_scale, film_shift, out_f32, out_t, save_s, mean, rstd, N, d,
               rows_per_batch > 0 ? rows_per_batch : N, eps, seed, stream, 0u, 1.f, g_seed_off, rope_cos, rope_sin,
               rope_out, rope_L};
@@ -725,6 +727,7 @@ FDDM_API int fddm_ln_bwd(int dy_dtype, const float* dout, const float* s, const 
                          float* dgamma, float* dbeta, float* dfilm_scale, float* dfilm_shift, long N, long d,
                          long rows_per_batch, float drop_p, unsigned long long seed, unsigned long long stream,
                          float* partials, void* hs) {
+  if (d <= 0) return (int)hipErrorInvalidValue;
   if (N <= 0) return 0;
   if (d > 64 * LN_MAXPL) return (int)hipErrorInvalidValue;
   // with FiLM, any parameter gradient makes ln_bwd_fused_kernel / ln_bwd_params_kernel add into both FiLM

@@ -587,25 +587,106 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, *, key_keep=None, dr
 
 
 # ----------------------------------------------------------------------------------- layernorm
+_LN_FWD_BUILDS = ((torch.float32, torch.bfloat16, torch.bfloat16), (torch.float32, torch.float32, torch.float32),
+                  (torch.bfloat16, torch.bfloat16, torch.bfloat16), (torch.float32, torch.float32, torch.bfloat16))
+_FLOATS = (torch.float32, torch.bfloat16)
+
+
+def _chk_rows(name, what, t, N, d, dtypes, dev):
+    """t is None or a contiguous [N, d] tensor of one of dtypes on dev (the kernels index it from a raw pointer)."""
+    _chk(t is None or (t.dim() == 2 and t.shape[0] == N and t.shape[1] == d and t.is_contiguous() and t.dtype in dtypes
+                       and t.device == dev),
+         f"{name}: {what} is contiguous [N, d], " + " or ".join(str(x)[6:] for x in dtypes) + ", on the input's GPU")
+
+
+def _chk_vec(name, what, t, n, dev, at_least=False):
+    """t is None or a contiguous f32 tensor of n elements (at_least: n or more) on dev."""
+    _chk(t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
+                       and (t.numel() >= n if at_least else t.numel() == n)),
+         f"{name}: {what} is contiguous float32 with {'>= ' if at_least else ''}{n} elements, on the input's GPU")
+
+
+def _chk_film(name, what, pair, N, d, rows_per_batch, dev):
+    """pair is None or two contiguous f32 [B, d] tensors with N == B rows_per_batch."""
+    if pair is None:
+        return
+    _chk(len(pair) == 2 and all(t is not None and t.dim() == 2 and t.shape[1] == d and t.dtype == torch.float32
+                                and t.is_contiguous() and t.device == dev for t in pair)
+         and pair[0].shape[0] == pair[1].shape[0], f"{name}: {what} is a pair of contiguous float32 [B, d], on the input's GPU")
+    _chk(rows_per_batch > 0 and pair[0].shape[0] * rows_per_batch == N, f"{name}: N == B * rows_per_batch for {what}")
+
+
 def ln_fwd(x, y, gamma, beta, *, out_f32=None, out_t=None, save_s=None, mean=None, rstd=None, film=None,
            rows_per_batch=0, eps=1e-5, drop_p=0.0, seed=0, rng_stream=0, rope=None):
-    """rope = (cos [L, d], sin [L, d], out bf16 [N, d], L): also write RoPE(output) — rope_fwd of the output — for the
+    """x [N, d] f32 / bf16, y None or [N, d], gamma / beta f32 [d], film = (scale, shift) f32 [B, d] with N == B
+    rows_per_batch; out_f32 / save_s f32 [N, d], out_t [N, d] in a dtype a build exists for ((x, y, out_t) = (f32, bf16,
+    bf16), (f32, f32, f32), (bf16, bf16, bf16), (f32, f32, bf16); without y its dtype counts as x's), mean / rstd f32, N
+    elements; d a multiple of 8 up to 1024; every tensor contiguous and on one GPU.
+    rope = (cos [>= L, d], sin [>= L, d], out bf16 [N, d], L): also write RoPE(output) — rope_fwd of the output — for the
     decoder's next block (f32 x, bf16 y and out_t, no FiLM)."""
+    _chk(x.dim() == 2 and x.is_contiguous() and x.dtype in _FLOATS and x.is_cuda, "ln_fwd: x is contiguous [N, d], float32 or bfloat16, on a GPU")
     N, d = x.shape
+    dev = x.device
+    _chk(d > 0 and d % 8 == 0 and d <= 1024, "ln_fwd: d is a multiple of 8 in [8, 1024]")
+    _chk_rows("ln_fwd", "y", y, N, d, _FLOATS, dev)
+    _chk_vec("ln_fwd", "gamma", gamma, d, dev)
+    _chk_vec("ln_fwd", "beta", beta, d, dev)
+    _chk(gamma is not None and beta is not None, "ln_fwd: gamma and beta are given")
+    _chk_film("ln_fwd", "film", film, N, d, rows_per_batch, dev)
+    _chk_rows("ln_fwd", "out_f32", out_f32, N, d, (torch.float32,), dev)
+    _chk_rows("ln_fwd", "save_s", save_s, N, d, (torch.float32,), dev)
+    _chk_rows("ln_fwd", "out_t", out_t, N, d, _FLOATS, dev)
+    _chk_vec("ln_fwd", "mean", mean, N, dev)
+    _chk_vec("ln_fwd", "rstd", rstd, N, dev)
+    ydt = y.dtype if y is not None else x.dtype
+    odt = out_t.dtype if out_t is not None else ydt
+    _chk((x.dtype, ydt, odt) in _LN_FWD_BUILDS, "ln_fwd: no build for these dtypes of x, y and out_t")
     fs, fh = film if film is not None else (None, None)
     rc, rs, ro, rl = rope if rope is not None else (None, None, None, 0)
-    out_code = code(out_t) if out_t is not None else code(x if y is None else y)
-    ycode = code(y) if y is not None else code(x)
-    call("fddm_ln_fwd", code(x), ycode, out_code, ptr(x), ptr(y), ptr(gamma), ptr(beta), ptr(fs), ptr(fh),
+    if rope is not None:
+        _chk(rl >= 1 and d % 16 == 0 and y is not None and film is None and
+             (x.dtype, ydt, odt) == _LN_FWD_BUILDS[0], "ln_fwd: rope needs f32 x, bf16 y and out_t, no film, d % 16 == 0, L >= 1")
+        _chk_rows("ln_fwd", "rope out", ro, N, d, (torch.bfloat16,), dev)
+        for t in (rc, rs):
+            _chk(t is not None and t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape[1] == d
+                 and t.shape[0] >= rl and t.device == dev, "ln_fwd: rope cos and sin are contiguous float32 [>= L, d]")
+    call("fddm_ln_fwd", code(x), code(y) if y is not None else code(x), code(out_t) if out_t is not None else
+         (code(y) if y is not None else code(x)), ptr(x), ptr(y), ptr(gamma), ptr(beta), ptr(fs), ptr(fh),
          ptr(out_f32), ptr(out_t), ptr(save_s), ptr(mean), ptr(rstd), N, d, rows_per_batch, float(eps), float(drop_p),
          seed, rng_stream, ptr(rc), ptr(rs), ptr(ro), rl, stream())
 
 
 def ln_bwd(dout, s, mean, rstd, gamma, beta, *, dres=None, dy_t=None, dgamma=None, dbeta=None, film_scale=None,
            dfilm=None, rows_per_batch=0, drop_p=0.0, seed=0, rng_stream=0, partials=None):
-    """partials: a LnPartials (ln_partials) collecting this LayerNorm's dgamma / dbeta slab sums for one ln_fold launch
+    """dout, s f32 [N, d] (d <= 1024), mean / rstd f32 with N elements, gamma / beta f32 [d]; dres f32 [N, d], dy_t
+    [N, d] f32 / bf16, dgamma / dbeta f32 [d] (added to), film_scale f32 [B, d] and dfilm = (dscale, dshift) f32 [B, d]
+    with N == B rows_per_batch; every tensor contiguous and on one GPU.
+    partials: a LnPartials (ln_partials) collecting this LayerNorm's dgamma / dbeta slab sums for one ln_fold launch
     (the fused pass only), or None: the sums are added to dgamma / dbeta with atomics."""
+    _chk(dout.dim() == 2 and dout.is_contiguous() and dout.dtype == torch.float32 and dout.is_cuda,
+         "ln_bwd: dout is contiguous float32 [N, d], on a GPU")
     N, d = dout.shape
+    dev = dout.device
+    _chk(0 < d <= 1024, "ln_bwd: d is in [1, 1024]")
+    _chk(s is not None and mean is not None and rstd is not None and gamma is not None, "ln_bwd: s, mean, rstd and gamma are given")
+    _chk_rows("ln_bwd", "s", s, N, d, (torch.float32,), dev)
+    _chk_vec("ln_bwd", "mean", mean, N, dev)
+    _chk_vec("ln_bwd", "rstd", rstd, N, dev)
+    _chk_vec("ln_bwd", "gamma", gamma, d, dev)
+    _chk_vec("ln_bwd", "beta", beta, d, dev)
+    _chk_rows("ln_bwd", "dres", dres, N, d, (torch.float32,), dev)
+    _chk_rows("ln_bwd", "dy_t", dy_t, N, d, _FLOATS, dev)
+    _chk_vec("ln_bwd", "dgamma", dgamma, d, dev)
+    _chk_vec("ln_bwd", "dbeta", dbeta, d, dev)
+    _chk((dgamma is None) == (dbeta is None), "ln_bwd: dgamma and dbeta come as a pair")
+    wants = dgamma is not None or dfilm is not None
+    _chk(not wants or beta is not None, "ln_bwd: parameter gradients need beta")
+    _chk(film_scale is not None or dfilm is None, "ln_bwd: dfilm needs film_scale")
+    if film_scale is not None:
+        _chk_film("ln_bwd", "film_scale", (film_scale, film_scale), N, d, rows_per_batch, dev)
+        _chk(not wants or dfilm is not None, "ln_bwd: with film_scale, parameter gradients need dfilm")
+        _chk_film("ln_bwd", "dfilm", dfilm, N, d, rows_per_batch, dev)
+        _chk(dfilm is None or dfilm[0].shape == film_scale.shape, "ln_bwd: dfilm has film_scale's shape")
     dfs, dfh = dfilm if dfilm is not None else (None, None)
     part = None
     if partials is not None:
@@ -627,6 +708,11 @@ class LnPartials:
         """dfilm = (dfs, dfh) [B, d] with FiLM batches of rows_per_batch rows: folded per batch when the batches
         are whole slabs (the fused pass); otherwise the backward adds them with atomics and leaves zeros here."""
         _chk(len(self.jobs) < 4, "at most 4 LayerNorms per fold")
+        _chk(N > 0 and 0 < d <= 1024, "LnPartials.add: N > 0 and d in [1, 1024]")
+        _chk(dgamma is not None and dbeta is not None and dgamma.is_cuda, "LnPartials.add: dgamma and dbeta are given, on a GPU")
+        _chk_vec("LnPartials.add", "dgamma", dgamma, d, dgamma.device)
+        _chk_vec("LnPartials.add", "dbeta", dbeta, d, dgamma.device)
+        _chk_film("LnPartials.add", "dfilm", dfilm, N, d, rows_per_batch, dgamma.device)
         rows = lib().fddm_ln_bwd_slab_rows()
         nslab = (N + rows - 1) // rows
         part = torch.empty(nslab, 4, d, device=dgamma.device, dtype=torch.float32)
@@ -835,8 +921,28 @@ def softmax_bwd_rows(y, dy, dz=None, accumulate=False):
     return dz
 
 
+def _chk_lfd(name, z, zt=None, vecs=()):
+    """z: contiguous f32 [B, C] on a GPU; zt: B C contiguous f32 / bf16 elements; vecs: (what, tensor, n) f32 with n elements
+    (None allowed where the kernel allows it)."""
+    _chk(z.dim() == 2 and z.dtype == torch.float32 and z.is_contiguous() and z.is_cuda,
+         f"{name}: the input is contiguous float32 [B, C], on a GPU")
+    B, C = z.shape
+    _chk(B > 0, f"{name}: B > 0")
+    _chk(zt is None or (zt.numel() == B * C and zt.is_contiguous() and zt.dtype in _FLOATS and zt.device == z.device),
+         f"{name}: z~ is contiguous [B, C], float32 or bfloat16, on the input's GPU")
+    for what, t, n in vecs:
+        _chk_vec(name, what, t, n, z.device)
+    return B, C
+
+
+def _chk_lfd_dtype(name, dt):
+    _chk(dt in _FLOATS, f"{name}: the output dtype is float32 or bfloat16")
+
+
 def lfd_std_fwd(z2d, out_dtype, eps=1e-5):
-    B, C = z2d.shape
+    """z~ = (z - mean_b z) / sqrt(var_b z + eps) [B, C] in out_dtype and inv_std f32 [C]: z2d contiguous f32 [B, C]."""
+    B, C = _chk_lfd("lfd_std_fwd", z2d)
+    _chk_lfd_dtype("lfd_std_fwd", out_dtype)
     zt = torch.empty(B, C, device=z2d.device, dtype=out_dtype)
     inv_std = torch.empty(C, device=z2d.device, dtype=torch.float32)
     call("fddm_lfd_std_fwd", code(zt), ptr(z2d), ptr(zt), ptr(inv_std), B, C, float(eps), stream())
@@ -844,21 +950,27 @@ def lfd_std_fwd(z2d, out_dtype, eps=1e-5):
 
 
 def lfd_std_bwd(dzt, zt, inv_std):
-    B, C = dzt.shape
+    """dz f32 [B, C] from dz~ (contiguous f32 [B, C]), z~ (B C contiguous f32 / bf16 elements) and inv_std f32 [C]."""
+    _chk(zt is not None and inv_std is not None, "lfd_std_bwd: z~ and inv_std are given")
+    B, C = _chk_lfd("lfd_std_bwd", dzt, zt, (("inv_std", inv_std, dzt.shape[-1]),))
     dz = torch.empty(B, C, device=dzt.device, dtype=torch.float32)
     call("fddm_lfd_std_bwd", code(zt), ptr(dzt), ptr(zt), ptr(inv_std), ptr(dz), B, C, stream())
     return dz
 
 
 def lfd_colstat(z2d, out, mean_sum=None, inv_n=0.0):
-    B, C = z2d.shape
-    _chk(out.numel() >= C and out.dtype == torch.float32, "lfd_colstat out")
+    """out[c] = sum_b z[b][c], or with mean_sum (f32 [C]) sum_b (z[b][c] - mean_sum[c] inv_n)^2: out f32, C elements."""
+    _chk(out is not None, "lfd_colstat: out is given")
+    B, C = _chk_lfd("lfd_colstat", z2d, None, (("out", out, z2d.shape[-1]), ("mean_sum", mean_sum, z2d.shape[-1])))
     call("fddm_lfd_colstat", ptr(z2d), ptr(out), ptr(mean_sum), float(inv_n), B, C, stream())
     return out
 
 
 def lfd_std_apply(z2d, out_dtype, s1, s2, inv_n, eps=1e-5):
-    B, C = z2d.shape
+    """z~ and inv_std from the global column sums s1 (sum z) and s2 (centred squares), f32 [C] each."""
+    _chk(s1 is not None and s2 is not None, "lfd_std_apply: s1 and s2 are given")
+    B, C = _chk_lfd("lfd_std_apply", z2d, None, (("s1", s1, z2d.shape[-1]), ("s2", s2, z2d.shape[-1])))
+    _chk_lfd_dtype("lfd_std_apply", out_dtype)
     zt = torch.empty(B, C, device=z2d.device, dtype=out_dtype)
     inv_std = torch.empty(C, device=z2d.device, dtype=torch.float32)
     call("fddm_lfd_std_apply", code(zt), ptr(z2d), ptr(zt), ptr(inv_std), ptr(s1), ptr(s2), float(inv_n), float(eps), B,
@@ -867,29 +979,42 @@ def lfd_std_apply(z2d, out_dtype, s1, s2, inv_n, eps=1e-5):
 
 
 def lfd_bwd_colstat(dzt, zt, out):
-    B, C = dzt.shape
-    _chk(out.numel() >= 2 * C and out.dtype == torch.float32, "lfd_bwd_colstat out")
+    """out[c] = sum_b dz~, out[C + c] = sum_b dz~ z~: out f32, 2 C elements."""
+    _chk(zt is not None and out is not None, "lfd_bwd_colstat: z~ and out are given")
+    B, C = _chk_lfd("lfd_bwd_colstat", dzt, zt, (("out", out, 2 * dzt.shape[-1]),))
     call("fddm_lfd_bwd_colstat", code(zt), ptr(dzt), ptr(zt), ptr(out), B, C, stream())
     return out
 
 
 def lfd_std_bwd_apply(dzt, zt, inv_std, sums, inv_n, scale=1.0):
-    B, C = dzt.shape
+    """dz = scale (dz~ - sums[c] inv_n - z~ sums[C + c] inv_n) inv_std: inv_std f32 [C], sums f32, 2 C elements."""
+    _chk(zt is not None and inv_std is not None and sums is not None, "lfd_std_bwd_apply: z~, inv_std and sums are given")
+    B, C = _chk_lfd("lfd_std_bwd_apply", dzt, zt, (("inv_std", inv_std, dzt.shape[-1]), ("sums", sums, 2 * dzt.shape[-1])))
     dz = torch.empty(B, C, device=dzt.device, dtype=torch.float32)
     call("fddm_lfd_std_bwd_apply", code(zt), ptr(dzt), ptr(zt), ptr(inv_std), ptr(sums), float(inv_n), float(scale),
          ptr(dz), B, C, stream())
     return dz
 
 
+def _chk_cm(name, Cm):
+    _chk(Cm.dim() == 2 and Cm.shape[0] == Cm.shape[1] and Cm.dtype == torch.float32 and Cm.is_contiguous() and Cm.is_cuda
+         and 0 < Cm.shape[0] <= 32768, f"{name}: Cm is contiguous float32 [D, D], 0 < D <= 32768, on a GPU")
+    return Cm.shape[0]
+
+
 def lfd_loss(Cm, lam):
-    D = Cm.shape[0]
+    """sum_j (1 - C_jj)^2 + lam sum_{j != k} C_jk^2 as an f32 scalar: Cm contiguous f32 [D, D]."""
+    D = _chk_cm("lfd_loss", Cm)
     loss = torch.empty((), device=Cm.device, dtype=torch.float32)
     call("fddm_lfd_loss", ptr(Cm), ptr(loss), D, float(lam), stream())
     return loss
 
 
 def lfd_dloss(Cm, gscale, lam, out_dtype):
-    D = Cm.shape[0]
+    """dC = gscale[0] d loss / dC [D, D] in out_dtype: gscale None (1) or one f32 element on Cm's GPU."""
+    D = _chk_cm("lfd_dloss", Cm)
+    _chk_vec("lfd_dloss", "gscale", gscale, 1, Cm.device)
+    _chk_lfd_dtype("lfd_dloss", out_dtype)
     dC = torch.empty(D, D, device=Cm.device, dtype=out_dtype)
     call("fddm_lfd_dloss", code(dC), ptr(Cm), ptr(gscale), ptr(dC), D, float(lam), stream())
     return dC

@@ -249,8 +249,8 @@ class _Dropper:
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         self.site += 1
-        if self.p <= 0:
-            return x
+        if self.p <= 0 or int(round(self.p * 65536.0)) == 0:
+            return x      # threshold 0 (p < 2^-17): the kernels' `if (thr16)` — nothing dropped, nothing scaled
         keep = _memo_mask(("e", self.seed, self.site, x.numel(), self.p),
                           lambda: dropout_keep(self.seed, self.site, x.numel(), self.p)).view(x.shape)
         return x * keep.float() * (1.0 / (1.0 - self.p))

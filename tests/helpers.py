@@ -2862,3 +2862,641 @@ def jump_peaked_case():
     z[r, (7 * r + 1) % V] = 0.0
     xt = torch.randint(0, V, (N,), generator=gen).numpy()
     return dict(logits=z, xt=xt, coef=jump_coefs(V, 1, False), coef_fast=jump_coefs(V, 1, True), V=V, N=N, L=L, seed=4242)
+
+
+# ----------------------------------------------- LayerNorm / FiLM (csrc/norm.hip) and L_fd (csrc/lfd.hip)
+# References, per-element error scales, inputs, emulations and case tables shared by tests/test_cpu_norm_lfd_ref.py
+# (which sets the constants below from the reference alone) and tests/test_gpu_norm_lfd_elem.py (which runs the kernels).
+# E: the fp32 evaluation in each kernel's own summation order (ln_fwd_emulate, ln_bwd_emulate, lfd_emulate: 8 elements
+# per lane, wave_sum_v's tree, the slab's 8-wave / 4-wave LDS combine, the fold's 16 groups, the column loops of
+# lfd.hip) against float64 in units of 2^-24 times the per-element scale, the maximum over every case below, measured
+# on the CPU (tests/test_cpu_norm_lfd_ref.py asserts measured <= stored <= 1.1 measured + NORM_E_FLOOR). The kernels are
+# allowed NORM_C = 8 E units (contraction, the device's sqrtf and division), hard cap 64.
+NORM_E = {"mean": 2.8, "rstd": 3.45, "out": 2.8, "dres": 3.85, "par": 3.85,
+          "lfd_is": 3.8, "lfd_zt": 4.4, "lfd_col": 6.15, "lfd_dz": 3.2, "lfd_loss": 1.55}
+NORM_C = {k: min(64.0, 8.0 * v) for k, v in NORM_E.items()}
+NORM_E_FLOOR = 0.05
+LN_EPS = 1e-5
+LN_SLAB = 32                   # rows per workgroup of ln_bwd_fused_kernel (norm.hip LNB_ROWS)
+LN_PROWS = 64                  # rows per workgroup of ln_bwd_params_kernel (norm.hip LNP_ROWS)
+LN_SEED, LN_STREAM = 20240611, 5
+LN_P = (0.1, 0.5, 2.0 ** -16, 1e-6, 0.0)       # thresholds 6554, 32768, 1, 0 (p > 0) and no dropout
+LN_TRIPLES = (("f32", "bf16", "bf16"), ("f32", "f32", "f32"), ("bf16", "bf16", "bf16"), ("f32", "f32", "bf16"))
+_TDT = {"f32": torch.float32, "bf16": torch.bfloat16}
+
+
+def ln_thr(p):
+    """norm.hip's thr16 = llrintf(p 65536) for p > 0 (round to nearest even of the fp32 product), else 0."""
+    return int(np.rint(np.float32(p) * np.float32(65536.0))) if p > 0 else 0
+
+
+def ln_drop_scale(p):
+    """The exact 1 / (1 - p) of the fp32 p where a threshold exists; 1 where thr16 = 0 (p = 0 and 0 < p < 2^-17: DESIGN
+    §2 — nothing is dropped, nothing is scaled). The kernel's fp32 1.f / (1.f - p) is within two roundings of it."""
+    return 1.0 / (1.0 - float(np.float32(p))) if ln_thr(p) else 1.0
+
+
+def ln_keep(N, d, p):
+    from oracle import fddm_oracle as O
+    if not ln_thr(p):
+        return torch.ones(N, d, dtype=torch.bool)
+    return O.dropout_keep(LN_SEED, LN_STREAM, N * d, p).view(N, d)
+
+
+def ln_fwd_dispatch(xdt, ydt, odt, hy, hf, d, rope=False):
+    """fddm_ln_fwd's choice of build (norm.hip): (x, y, out dtype, HY, HF, CH, RP), or None where it refuses."""
+    if d <= 0 or d > 1024 or d % 8:
+        return None
+    ch = 1 if d <= 512 else 2
+    if rope:
+        if (xdt, ydt, odt) != LN_TRIPLES[0] or not hy or hf or d % 16:
+            return None
+        return (xdt, ydt, odt, True, False, ch, True)
+    return (xdt, ydt, odt, hy, hf, ch, False) if (xdt, ydt, odt) in LN_TRIPLES else None
+
+
+def ln_fwd_codes(xdt, ydt, odt):
+    """The dtype triple ops.ln_fwd passes for x, y (None: absent) and out_t (always given here)."""
+    return (xdt, ydt if ydt is not None else xdt, odt)
+
+
+# every build ops.ln_fwd can launch: without y the y code is x's, so (f32, bf16, bf16) exists only with HY
+LN_FWD_BUILDS = tuple((*tr, hy, hf, ch, False) for tr in LN_TRIPLES for hy in (True, False) for hf in (True, False)
+                      for ch in (1, 2) if hy or tr[0] == tr[1]) + tuple((*LN_TRIPLES[0], True, False, ch, True) for ch in (1, 2))
+
+
+def ln_fwd_cases():
+    """dicts: id, tr (dtype triple), hy, hf, N, d, L (rows per FiLM batch, 0: none), p, rope (L of the tables, 0: none),
+    alias (save_s in place over x), k0 (the first row's kind, ln_rows)."""
+    out = []
+    D1, D2, NS, BL = (8, 200, 512), (520, 1024), (1, 5, 33, 70), ((5, 1), (2, 20), (2, 32), (2, 37))
+
+    def add(tr, hy, hf, N, d, L, p, rope=0, alias=False):
+        i = len(out)
+        out.append(dict(id=f"{i:02d}-{'-'.join(tr)}-{'y' if hy else 'n'}{'f' if hf else 'n'}-N{N}-d{d}-L{L}-p{p:.2g}"
+                        + ("-rope" if rope else "") + ("-alias" if alias else ""),
+                        tr=tr, hy=hy, hf=hf, N=N, d=d, L=L, p=p, rope=rope, alias=alias, k0=i))
+    for tr in LN_TRIPLES:
+        for hy in (True, False):
+            for hf in (True, False):
+                for ch in (1, 2):
+                    if not hy and tr[0] != tr[1]:
+                        continue
+                    i = len(out)
+                    d = D1[i % 3] if ch == 1 else D2[i % 2]
+                    B, L = BL[i % 4] if hf else (NS[i % 4], 0)
+                    add(tr, hy, hf, B * L if hf else B, d, L, LN_P[i % 5] if hy else 0.0, alias=tr[0] == "f32" and i % 3 == 0)
+    add(LN_TRIPLES[0], True, False, 18, 128, 0, 0.1, rope=9)
+    add(LN_TRIPLES[0], True, False, 10, 528, 0, 0.5, rope=5)
+    for j, p in enumerate(LN_P):                       # every p with every row kind, at the tail shapes
+        add(LN_TRIPLES[j % 4], True, j % 2 == 0, 14 if j % 2 else 74, (200, 520)[j % 2], 0 if j % 2 else 37, p)
+    add(LN_TRIPLES[1], True, True, 2 * 576, 8, 576, 0.1)
+    add(LN_TRIPLES[2], True, True, 64, 512, 32, 0.5)
+    add(LN_TRIPLES[0], True, False, 1, 512, 0, 0.1)
+    add(LN_TRIPLES[3], False, False, 1, 1024, 0, 0.0)
+    add(LN_TRIPLES[1], False, False, 70, 8, 0, 0.0)
+    add(LN_TRIPLES[2], False, False, 33, 520, 0, 0.0)
+    add(LN_TRIPLES[1], False, False, 14, 200, 0, 0.0)
+    return out
+
+
+LN_KINDS = ("flat", "offset", "outlier", "const", "zero", "tiny", "flat")
+
+
+def ln_rows(gen, N, d, k0, hy):
+    """x, y [N, d] f32: randn times a power of two per row and per column; row r is of kind LN_KINDS[(r + k0) % 7]:
+    offset = a common offset of 64 row standard deviations, outlier = one channel 2^8 above the loudest, const, zero,
+    tiny = 2^-20-sized values. y is nowhere zero (|y| >= 0.05 of its scale); on const and zero rows it is 2^-30-sized, so
+    that the row's fp32 sum x + y is x (variance 0 in the kernel, < 2^-58 in the reference: rstd = eps^-1/2 either way)."""
+    rp, cp = _pow2(gen, N), _pow2(gen, d)
+    sc = rp[:, None] * cp[None, :]
+    x = torch.randn(N, d, generator=gen) * sc
+    y = (torch.randn(N, d, generator=gen).abs() + 0.05) * (torch.randint(0, 2, (N, d), generator=gen) * 2.0 - 1.0) * sc
+    kind = (torch.arange(N) + k0) % 7
+    xo = x[kind == 1]
+    x[kind == 1] += 64.0 * (xo - xo.mean(1, keepdim=True)).pow(2).mean(1, keepdim=True).sqrt().clamp_min(rp[kind == 1, None])
+    r = torch.nonzero(kind == 2)[:, 0]
+    x[r, (7 * r) % d] = 2.0 ** 8 * 4.0 * rp[r]
+    x[kind == 3] = (1.5 * rp[kind == 3])[:, None].expand(-1, d)
+    x[kind == 4] = 0.0
+    x[kind == 5] *= 2.0 ** -20
+    y[(kind == 3) | (kind == 4)] *= 2.0 ** -30
+    y[kind == 5] *= 2.0 ** -20
+    return x, (y if hy else None), kind
+
+
+def ln_affine(gen, d, B=0):
+    """gamma (zeros at c % 5 = 2, negative entries), beta; with B: FiLM scale [B, d] (exactly -1 at c % 7 = 1, +-4 at
+    c % 11 = 3) and shift."""
+    gamma, beta = torch.randn(d, generator=gen), 0.5 * torch.randn(d, generator=gen)
+    gamma[2::5] = 0.0
+    if d > 1:
+        gamma[1::4] = -gamma[1::4].abs()
+    if not B:
+        return gamma, beta, None
+    fs, fh = 0.5 * torch.randn(B, d, generator=gen), torch.randn(B, d, generator=gen)
+    fs[:, 1::7] = -1.0
+    fs[:, 3::11] = 4.0 * torch.sign(fs[:, 3::11] + 1e-9)
+    return gamma, beta, (fs.contiguous(), fh.contiguous())
+
+
+@functools.lru_cache(maxsize=None)
+def ln_fwd_operands(i):
+    """x, y in their storage dtypes (y None without HY), gamma, beta, film or None, keep [N, d], (cos, sin) or None."""
+    from oracle import fddm_oracle as O
+    c = ln_fwd_cases()[i]
+    gen = _gen(8100, i)
+    x, y, kind = ln_rows(gen, c["N"], c["d"], c["k0"], c["hy"])
+    gamma, beta, film = ln_affine(gen, c["d"], c["N"] // c["L"] if c["hf"] else 0)
+    x = x.to(_TDT[c["tr"][0]])
+    y = y.to(_TDT[c["tr"][1]]) if y is not None else None
+    rope = None
+    if c["rope"]:
+        cos, sin = O.rope_cos_sin(c["N"], O.rope_inv_freq(c["d"]))      # the kernel reads the first c["rope"] rows
+        rope = (cos.contiguous(), sin.contiguous())
+    return x, y, gamma, beta, film, ln_keep(c["N"], c["d"], c["p"]), rope, kind
+
+
+def ln_fwd_ref64(x, y, gamma, beta, film, L, p, keep, *, eps=LN_EPS, rope=None, rope_L=0, mut=None):
+    """float64 on the operands as stored. v = x + y keep / (1 - p), m, rstd = (var + eps)^-1/2, out = (v - m) rstd gamma
+    + beta (then (1 + fs[b]) . + fh[b], b = row // L), and per element the scale each may be wrong by, in units of u:
+      s     sv = 3 |t| + |v|  (t = y keep / (1 - p): 1 - p, the quotient, the product; then the add; with or without
+            contraction); |v| without dropout; 0 without y (a copy)
+      mean  M = mean_j (|v_j| + sv_j)
+      rstd  rstd (1 + rstd^2 mean_j (|v_j - m| sv_j)): its own roundings, and d var = 2 mean (v - m) dv
+      out   |gamma| (rstd (|v - m| + M + sv) + |v - m| u_rstd) + |beta|, through FiLM times |1 + fs|, plus |fh|
+    `mut` builds the mutants of tests/test_cpu_norm_lfd_ref.py."""
+    N, d = x.shape
+    xd = x.double()
+    thr = ln_thr(p)
+    if y is None:
+        v, sv = xd, torch.zeros_like(xd)
+    elif thr == 0:
+        v = xd + y.double()
+        sv = v.abs()
+    else:
+        k = keep.reshape(-1).roll(-1).view(N, d) if mut == "mask_next" else keep
+        t = y.double() * k.double() * (1.0 if mut == "noscale" else ln_drop_scale(p))
+        v = xd + t
+        sv = 3.0 * t.abs() + v.abs()
+    m = v.mean(1, keepdim=True)
+    c = v - m
+    var = (c * c).mean(1, keepdim=True)
+    if mut == "unbiased":
+        var = var * d / max(d - 1, 1)
+    elif mut == "onepass":                              # fp32 E[v^2] - m^2
+        v32 = v.float()
+        m32 = v32.mean(1, keepdim=True)
+        m, var = m32.double(), ((v32 * v32).mean(1, keepdim=True) - m32 * m32).double().clamp_min(0.0)
+        c = v - m
+    elif mut == "tail":                                 # the lanes past the row end count the chunk they re-loaded
+        n = 64 * (1 if d <= 512 else 2) - d // 8
+        m = (v.sum(1, keepdim=True) + n * v[:, -8:].sum(1, keepdim=True)) / d
+        c = v - m
+        var = ((c * c).sum(1, keepdim=True) + n * (c[:, -8:] ** 2).sum(1, keepdim=True)) / d
+    rstd = 1.0 / (var.sqrt() + eps) if mut == "eps_out" else 1.0 / torch.sqrt(var + eps)
+    M = (v.abs() + sv).mean(1, keepdim=True)
+    u_rstd = rstd * (1.0 + rstd ** 2 * (c.abs() * sv).mean(1, keepdim=True))
+    g, b = gamma.double()[None, :], beta.double()[None, :]
+    out = c * rstd * g + b
+    u_out = g.abs() * (rstd * (c.abs() + M + sv) + c.abs() * u_rstd) + b.abs()
+    if film is not None:
+        row = torch.arange(N)
+        bi = ((row - 1).clamp_min(0) if mut == "film_prev" else row) // L
+        fs, fh = film[0].double()[bi], film[1].double()[bi]
+        f1 = fs if mut == "fs" else 1.0 + fs
+        out = out * f1 + fh
+        u_out = u_out * f1.abs() + fh.abs()
+    r = Ref(s=v, u_s=sv, mean=m[:, 0], u_mean=M[:, 0], rstd=rstd[:, 0], u_rstd=u_rstd[:, 0], out=out, u_out=u_out)
+    r.b_s = U24 * sv * (1.0 + 2.0 ** -20)
+    r.b_mean, r.b_rstd, r.b_out = NORM_C["mean"] * U24 * r.u_mean, NORM_C["rstd"] * U24 * r.u_rstd, NORM_C["out"] * U24 * u_out
+    r.b_out_bf = bf16_round_bound(out, r.b_out)
+    if rope is not None:
+        pos = torch.arange(N) if mut == "rope_pos" else None
+        q = rope_fwd_ref64(out, rope[0], rope[1], rope_L, pos=pos, sin_sign=-1.0 if mut == "rope_sign" else 1.0)
+        pm = _rope_pos(N, rope_L, None)
+        ca, sa = rope[0].double()[pm].abs(), rope[1].double()[pm].abs()
+        b1, b2 = r.b_out[:, 0::2], r.b_out[:, 1::2]
+        carried = torch.cat([b1 * ca[:, 0::2] + b2 * sa[:, 1::2], b1 * sa[:, 0::2] + b2 * ca[:, 1::2]], 1)
+        r.rope, r.b_rope = q.out, bf16_round_bound(q.out, q.b + carried)
+    return r
+
+
+def _tree64(t):
+    """wave_sum_v (norm.hip): lanes l and l ^ 1, ^ 2, ^ 4 (row_half_mirror of equal quads), ^ 8 (row_mirror), ^ 16, ^ 32
+    (the permlane swaps), every addend pair the same on both lanes: six rounds of adjacent pairs. t [..., 64] fp32."""
+    for _ in range(6):
+        t = t[..., 0::2] + t[..., 1::2]
+    return t[..., 0]
+
+
+def _seq(t):
+    """Sum over the last axis, one fp32 accumulator from 0 in index order."""
+    acc = torch.zeros(t.shape[:-1], dtype=t.dtype)
+    for j in range(t.shape[-1]):
+        acc = acc + t[..., j]
+    return acc
+
+
+def ln_rowsum32(t, vec):
+    """A row sum of t [N, d] fp32 as the kernels take it. vec: a lane adds the 8 elements of chunk lane, then of chunk
+    lane + 64 (ln_fwd_kernel, ln_bwd_fused_kernel); else elements lane, lane + 64, ... (ln_bwd_kernel); then the tree."""
+    N, d = t.shape
+    if vec:
+        ch = 1 if d <= 512 else 2
+        p = torch.zeros(N, ch * 512)
+        p[:, :d] = t
+        lanes = p.view(N, ch, 64, 8).permute(0, 2, 1, 3).reshape(N, 64, ch * 8)
+    else:
+        p = torch.zeros(N, 1024)
+        p[:, :d] = t
+        lanes = p.view(N, 16, 64).permute(0, 2, 1)
+    return _tree64(_seq(lanes))
+
+
+def ln_fwd_emulate(x, y, gamma, beta, film, L, p, keep, eps=LN_EPS, fma=False):
+    """ln_fwd_kernel in fp32 on the CPU: s, mean, rstd, out. fma: the dropout product through an FMA."""
+    N, d = x.shape
+    v = x.float()
+    if y is not None:
+        if ln_thr(p):
+            ds = (np.float32(1.0) / (np.float32(1.0) - np.float32(p))).item()
+            ds = torch.tensor(ds, dtype=torch.float32)
+            kf = keep.float()
+            v = _fma32(y.float() * kf, ds.expand(N, d), v) if fma else v + y.float() * kf * ds
+        else:
+            v = v + y.float()
+    fd = torch.tensor(float(d), dtype=torch.float32)
+    mean = (ln_rowsum32(v, True) / fd)[:, None]
+    t = v - mean
+    var = ln_rowsum32(t * t, True) / fd
+    rstd = (1.0 / torch.sqrt(var + torch.tensor(eps, dtype=torch.float32)))[:, None]
+    o = (v - mean) * rstd * gamma[None, :] + beta[None, :]
+    if film is not None:
+        bi = torch.arange(N) // L
+        o = o * (1.0 + film[0][bi]) + film[1][bi]
+    return v, mean[:, 0], rstd[:, 0], o
+
+
+# ---- LayerNorm backward
+def ln_bwd_dispatch(d, N, L, film, params, aligned=True, beta=True):
+    """fddm_ln_bwd's choice (norm.hip): ("fused", CH) or ("rows",) / ("rows", "params")."""
+    vec_ok = d % 8 == 0 and d <= 1024 and aligned
+    rpb = L if L > 0 else N
+    if params and (not film or rpb % LN_SLAB == 0) and beta and vec_ok:
+        return ("fused", 1 if d <= 512 else 2)
+    return ("rows", "params") if params else ("rows",)
+
+
+# (kernel, dy dtype, partials, FiLM): the fused builds; ("rows", dy dtype, with ln_bwd_params_kernel): the two-pass form
+LN_BWD_BUILDS = tuple((("fused", ch), dt, part, film) for ch in (1, 2) for dt in ("f32", "bf16") for part in (False, True)
+                      for film in (False, True)) + tuple(("rows", dt, par) for dt in ("f32", "bf16") for par in (False, True))
+
+
+def ln_bwd_cases():
+    """dicts: id, d, N, L (0: no FiLM), dt (dy_t's dtype), p, part (LnPartials), params (parameter gradients wanted),
+    off4 (dres one float into its buffer: the unvectorised path)."""
+    out = []
+
+    def add(d, N, L, dt, p, part=False, params=True, off4=False):
+        i = len(out)
+        out.append(dict(id=f"{i:02d}-d{d}-N{N}-L{L}-{dt}-p{p:.2g}" + ("-part" if part else "") + ("" if params else "-nopar")
+                        + ("-off4" if off4 else ""), d=d, N=N, L=L, dt=dt, p=p, part=part, params=params, off4=off4, k0=i))
+    D1, D2, NS, BL = (8, 200, 512), (520, 1024), (1, 5, 33, 70), ((2, 32), (3, 32))
+    for ch in (1, 2):
+        for dt in ("f32", "bf16"):
+            for part in (False, True):
+                for film in (False, True):
+                    i = len(out)
+                    d = D1[i % 3] if ch == 1 else D2[i % 2]
+                    B, L = BL[i % 2] if film else (NS[i % 4], 0)
+                    add(d, B * L if film else B, L, dt, LN_P[i % 5], part)
+    add(200, 1100, 0, "bf16", 0.1, True)               # 35 slabs: three fold rounds, a ragged last slab
+    add(200, 1100, 0, "f32", 0.5, False)
+    add(8, 2 * 576, 576, "bf16", 0.1, True)            # 18 slabs per FiLM batch: fold group 15 exists
+    add(8, 70, 0, "f32", 2.0 ** -16, True)
+    add(520, 70, 0, "bf16", 1e-6, False)
+    add(100, 70, 0, "f32", 0.1)                        # the two-pass form: d % 8 != 0
+    add(100, 33, 0, "bf16", 0.5, params=False)
+    add(1, 5, 0, "f32", 0.0)
+    add(1, 70, 1, "bf16", 0.1)
+    add(200, 5, 1, "f32", 0.1)                         # FiLM, a batch per row
+    add(512, 40, 20, "bf16", 0.5)                      # FiLM, batches inside a slab
+    add(8, 74, 37, "f32", 1e-6)                        # FiLM, a 64-row params workgroup over two batches
+    add(200, 33, 0, "f32", 0.1, off4=True)
+    add(200, 5, 0, "bf16", 0.0, params=False, off4=True)
+    add(100, 5, 0, "f32", 0.1, params=False)
+    return out
+
+
+def ln_bwd_build(c):
+    k = ln_bwd_dispatch(c["d"], c["N"], c["L"], c["L"] > 0, c["params"], not c["off4"])
+    return (k, c["dt"], c["part"], c["L"] > 0) if k[0] == "fused" else ("rows", c["dt"], len(k) == 2)
+
+
+@functools.lru_cache(maxsize=None)
+def ln_bwd_operands(i):
+    """dout, s, mean, rstd (f32: the float64 statistics of s, rounded), gamma, beta, fs or None, keep, old (dgamma, dbeta,
+    dfs, dfh: non-zero)."""
+    c = ln_bwd_cases()[i]
+    N, d, L = c["N"], c["d"], c["L"]
+    gen = _gen(8200, i)
+    s, _, kind = ln_rows(gen, N, d, c["k0"], False)
+    B = N // L if L else 0
+    gamma, beta, film = ln_affine(gen, d, B)
+    dout = torch.randn(N, d, generator=gen) * _pow2(gen, N)[:, None] * _pow2(gen, d)[None, :]
+    sd = s.double()
+    mean = sd.mean(1)
+    rstd = 1.0 / torch.sqrt(sd.var(1, unbiased=False) + LN_EPS)
+    old = [torch.randn(d, generator=gen), torch.randn(d, generator=gen)]
+    old += [torch.randn(B, d, generator=gen), torch.randn(B, d, generator=gen)] if L else [None, None]
+    return dout, s, mean.float(), rstd.float(), gamma, beta, film[0] if film else None, ln_keep(N, d, c["p"]), old, kind
+
+
+def ln_bwd_ref64(dout, s, mean, rstd, gamma, beta, fs, L, p, keep, old, *, mut=None):
+    """The kernels' formula in float64 on the stored s, mean, rstd: xh = (s - mean) rstd, g' = dout (1 + fs[b]),
+    gx = g' gamma, dres = rstd (gx - mean_j gx - xh mean_j (gx xh)), dy = dres keep / (1 - p); dgamma = old + sum_r g' xh,
+    dbeta = old + sum_r g', dfs[b] = old + sum_{r in b} dout (xh gamma + beta), dfh[b] = old + sum_{r in b} dout. Scales:
+    rstd (|gx| + mean |gx| + |xh| mean |gx xh|) and the absolute sums."""
+    N, d = dout.shape
+    xh = (s.double() - mean.double()[:, None]) * rstd.double()[:, None]
+    g0 = dout.double()
+    gm, bt = gamma.double()[None, :], beta.double()[None, :]
+    bi = torch.arange(N) // L if fs is not None else None
+    g = g0 * (1.0 + fs.double()[bi]) if fs is not None else g0
+    gx = g * gm
+    s1 = gx.mean(1, keepdim=True)
+    s2 = (gx * xh).mean(1, keepdim=True)
+    rs = rstd.double()[:, None]
+    dres = rs * (gx - (0.0 if mut == "no_s1" else s1) - xh * (s2.roll(-1, 0) if mut == "s2_next" else s2))
+    u_dres = rs * (gx.abs() + gx.abs().mean(1, keepdim=True) + xh.abs() * (gx * xh).abs().mean(1, keepdim=True))
+    ds = ln_drop_scale(p)
+    r = Ref(dres=dres, u_dres=u_dres, b_dres=NORM_C["dres"] * U24 * u_dres)
+    r.dy = dres * keep.double() * ds
+    b_dy = (r.b_dres * ds + 3.0 * U24 * r.dy.abs()) * keep.double()
+    r.b_dy = {"f32": b_dy, "bf16": torch.where(keep, bf16_round_bound(r.dy, b_dy), torch.zeros_like(b_dy))}
+    rows = torch.ones(N, 1, dtype=torch.float64)
+    if mut == "ragged":
+        rows[(N // LN_SLAB) * LN_SLAB:] = 0.0
+    elif mut == "fold15":                               # the fold's sixteenth group: slabs 15, 31, ... (of the batch)
+        slab = torch.arange(N) // LN_SLAB
+        rows[(slab % 16) == 15] = 0.0
+    o = [torch.zeros_like(t) if mut == "no_old" else t.double() for t in old if t is not None]
+    gg = g0 if mut == "dgamma_nofs" else g
+    r.dgamma, r.u_dgamma = o[0] + (gg * xh * rows).sum(0), o[0].abs() + (g * xh).abs().sum(0)
+    db = (g * rows).sum(0)
+    r.dbeta, r.u_dbeta = o[1] + (db.roll(-1) if mut == "dbeta_next" else db), o[1].abs() + g.abs().sum(0)
+    if fs is not None:
+        B = fs.shape[0]
+        if mut == "fold15":
+            rows = torch.ones(N, 1, dtype=torch.float64)
+            rows[((torch.arange(N) % L) // LN_SLAB) % 16 == 15] = 0.0
+        lin = xh * gm + (0.0 if mut == "dfs_nobeta" else bt)
+        r.dfs = o[2] + (g0 * lin * rows).view(B, L, d).sum(1)
+        r.u_dfs = o[2].abs() + (g0.abs() * ((xh * gm).abs() + bt.abs())).view(B, L, d).sum(1)
+        r.dfh = o[3] + (g0 * rows).view(B, L, d).sum(1)
+        r.u_dfh = o[3].abs() + g0.abs().view(B, L, d).sum(1)
+    for n in ("dgamma", "dbeta", "dfs", "dfh"):
+        if hasattr(r, n):
+            setattr(r, "b_" + n, NORM_C["par"] * U24 * getattr(r, "u_" + n))
+    return r
+
+
+def _slab_sums32(t, L):
+    """ln_bwd_fused_kernel's per-slab column sums of t [N, d] fp32: wave w adds rows w, w + 8, w + 16, w + 24 in order,
+    waves w and w + 4 are added, then the four in order. [nslab, d]."""
+    N, d = t.shape
+    ns = (N + LN_SLAB - 1) // LN_SLAB
+    p = torch.zeros(ns * LN_SLAB, d)
+    p[:N] = t
+    w = _seq(p.view(ns, 4, 8, d).permute(0, 2, 3, 1))                   # [ns, 8, d]
+    w = w[:, :4] + w[:, 4:]
+    return _seq(w.permute(0, 2, 1))
+
+
+def _fold32(part, old):
+    """ln_fold_kernel: group g adds slabs g, g + 16, ... in order, the 16 groups are added in order, then onto old."""
+    ns, d = part.shape
+    p = torch.zeros(((ns + 15) // 16) * 16, d)
+    p[:ns] = part
+    return old + _seq(_seq(p.view(-1, 16, d).permute(1, 2, 0)).permute(1, 0))
+
+
+def ln_bwd_emulate(dout, s, mean, rstd, gamma, beta, fs, L, kernel, old, part):
+    """The backward in fp32: dres, and the four parameter sums added to old. kernel: ln_bwd_dispatch's answer. Fused: slab
+    sums, then the fold (part) or one atomic per slab in slab order; two-pass: 64-row chunks (cut at FiLM batches for
+    the FiLM sums), one atomic each, in order."""
+    N, d = dout.shape
+    x = (s - mean[:, None]) * rstd[:, None]
+    g0 = dout
+    bi = torch.arange(N) // L if fs is not None else None
+    g = g0 * (1.0 + fs[bi]) if fs is not None else g0
+    gx = g * gamma[None, :]
+    vec = kernel[0] == "fused"
+    fd = torch.tensor(float(d), dtype=torch.float32)
+    s1 = (ln_rowsum32(gx, vec) / fd)[:, None]
+    s2 = (ln_rowsum32(gx * x, vec) / fd)[:, None]
+    dres = rstd[:, None] * (gx - s1 - x * s2)
+    terms = [g * x, g] + ([g0 * (x * gamma[None, :] + beta[None, :]), g0] if fs is not None else [])
+    outs = []
+    for q, t in enumerate(terms):
+        groups = [(0, N)] if q < 2 else [(b * L, (b + 1) * L) for b in range(N // L)]
+        res = []
+        for lo, hi in groups:
+            o = old[q] if q < 2 else old[q][lo // L]
+            if vec:
+                ps = _slab_sums32(t[lo:hi], L)
+                o = _fold32(ps, o) if part else _seq(torch.cat([o[None], ps]).permute(1, 0))
+            else:
+                cuts = sorted(set(range(lo, hi, 1)) & (set(range(0, N, LN_PROWS)) | {lo}))
+                for a in cuts:
+                    e = min(hi, (a // LN_PROWS + 1) * LN_PROWS)
+                    o = o + _seq(t[a:e].permute(1, 0))
+            res.append(o)
+        outs.append(res[0] if q < 2 else torch.stack(res))
+    return dres, outs
+
+
+# ---- L_fd
+LFD_BC = ((1, 257), (2, 1000), (3, 1), (32, 257), (33, 1000), (3, 257))
+LFD_D = ((1, False), (33, False), (256, False), (1030, False), (256, True))          # (D, a view 4 bytes into its buffer)
+LFD_LAM = (0.0, 5e-3)
+LFD_W = 0.375                  # lfd_std_bwd_apply's scale (1 / world size times the loss weight: any value)
+LFD_RANKS = 3                  # the data-parallel kernels see one rank's rows of a batch LFD_RANKS times as large
+
+
+@functools.lru_cache(maxsize=None)
+def lfd_operands(B, C):
+    """z, dz~ [B, C] f32, z~ [B, C] (f32; the bf16 case rounds it), inv_std [C], and for the data-parallel kernels the
+    global sums s1, s2 [C] and backward sums [2 C] of a batch of LFD_RANKS B rows. Columns: a power of two per row and
+    per column; column c of kind c % 5: 1 = an offset of 2^6 spreads, 2 = constant."""
+    gen = _gen(8300, B, C)
+    sc = _pow2(gen, B)[:, None] * _pow2(gen, C)[None, :]
+    z = torch.randn(B, C, generator=gen) * sc
+    kind = torch.arange(C) % 5
+    z[:, kind == 1] += 64.0 * _pow2(gen, C)[None, kind == 1] * 4.0
+    z[:, kind == 2] = (1.5 * _pow2(gen, C))[None, kind == 2].expand(B, -1)
+    dzt = torch.randn(B, C, generator=gen) * sc
+    zt = torch.randn(B, C, generator=gen)
+    zt[:, kind == 2] = 0.0
+    inv = 1.0 / (torch.rand(C, generator=gen) * 4.0 + 0.01)
+    n = LFD_RANKS * B
+    rest = torch.randn(n - B, C, generator=gen) * _pow2(gen, C)[None, :] + z.mean(0, keepdim=True)
+    allz = torch.cat([z, rest]).double()
+    s1 = allz.sum(0).float()
+    s2 = ((allz - allz.mean(0, keepdim=True)) ** 2).sum(0).float()
+    sums = torch.cat([dzt.double().sum(0) * LFD_RANKS, (dzt.double() * zt.double()).sum(0) * LFD_RANKS]).float()
+    return z, dzt, zt, inv, s1, s2, sums
+
+
+def lfd_std_ref64(z, eps=LN_EPS, *, s1=None, s2=None, inv_n=None, mut=None):
+    """z~ = (z - m) is, is = (var + eps)^-1/2 over the batch (lfd_std_fwd), or from the stored global sums m = s1 inv_n,
+    var = s2 inv_n (lfd_std_apply). Scales: is (relative); is (|z - m| + mean_b |z|), with |m| for the mean of |z| in the
+    apply form (m is read, not summed)."""
+    zd = z.double()
+    B = z.shape[0]
+    if s1 is None:
+        m = zd.mean(0, keepdim=True)
+        var = ((zd - m) ** 2).sum(0, keepdim=True) / (max(B - 1, 1) if mut == "unbiased" else B)
+        ma = zd.abs().mean(0, keepdim=True)
+    else:
+        n = float(np.float32(1.0 / B if mut == "localB" else inv_n))
+        m, var = s1.double()[None, :] * n, s2.double()[None, :] * n
+        ma = m.abs()
+    is_ = 1.0 / torch.sqrt(var + eps)
+    zt = (zd - m) * is_
+    u_zt = is_ * ((zd - m).abs() + ma)
+    r = Ref(inv=is_[0], b_inv=NORM_C["lfd_is"] * U24 * is_[0], zt=zt, u_zt=u_zt, b_zt=NORM_C["lfd_zt"] * U24 * u_zt)
+    r.b_zt_bf = bf16_round_bound(zt, r.b_zt)
+    return r
+
+
+def lfd_colstat_ref64(z, s1=None, inv_n=None):
+    """pass 1: sum_b z, scale sum |z|; pass 2: sum_b t^2, t = z - s1 inv_n on the stored s1, scale sum |t| (|t| + |m|)."""
+    zd = z.double()
+    if s1 is None:
+        return Ref(out=zd.sum(0), u=zd.abs().sum(0), b=NORM_C["lfd_col"] * U24 * zd.abs().sum(0))
+    m = s1.double()[None, :] * float(np.float32(inv_n))
+    t = zd - m
+    u = (t.abs() * (t.abs() + m.abs())).sum(0)
+    return Ref(out=(t * t).sum(0), u=u, b=NORM_C["lfd_col"] * U24 * u)
+
+
+def lfd_bwd_ref64(dzt, zt, inv, *, sums=None, inv_n=None, scale=1.0, mut=None):
+    """dz = W is (g - m1 - z~ m2) on the stored z~ and inv_std: m1, m2 the batch means of g and g z~ (lfd_std_bwd, W = 1)
+    or sums inv_n (lfd_std_bwd_apply). Also the column sums of lfd_bwd_colstat. Scales: the absolute evaluation."""
+    g, z = dzt.double(), zt.double()
+    B, C = g.shape
+    if sums is None:
+        m1, m2 = g.mean(0, keepdim=True), (g * z).mean(0, keepdim=True)
+        a1, a2 = g.abs().mean(0, keepdim=True), (g * z).abs().mean(0, keepdim=True)
+    else:
+        n = float(np.float32(1.0 / B if mut == "localB" else inv_n))
+        m1, m2 = sums.double()[None, :C] * n, sums.double()[None, C:] * n
+        a1, a2 = m1.abs(), m2.abs()
+    W = 1.0 if mut == "noW" else float(np.float32(scale))
+    is_ = inv.double()[None, :]
+    dz = W * is_ * (g - m1 - z * (0.0 if mut == "no_m2" else m2))
+    u = abs(W) * is_ * (g.abs() + a1 + z.abs() * a2)
+    cs = torch.cat([g.sum(0), (g * z).sum(0)])
+    u_cs = torch.cat([g.abs().sum(0), (g * z).abs().sum(0)])
+    return Ref(dz=dz, u_dz=u, b_dz=NORM_C["lfd_dz"] * U24 * u, cs=cs, u_cs=u_cs, b_cs=NORM_C["lfd_col"] * U24 * u_cs)
+
+
+def lfd_emulate(z, dzt, zt, inv, s1, s2, sums, inv_n, scale, eps=LN_EPS):
+    """lfd.hip's column loops in fp32: a dict of every kernel's outputs."""
+    B = z.shape[0]
+    fB = torch.tensor(float(B), dtype=torch.float32)
+    n = torch.tensor(inv_n, dtype=torch.float32)
+    e = torch.tensor(eps, dtype=torch.float32)
+    col = lambda t: _seq(t.permute(1, 0))
+    m = col(z) / fB
+    var = col((z - m) ** 2) / fB
+    is_ = 1.0 / torch.sqrt(var + e)
+    o = dict(inv=is_, zt=(z - m) * is_, c1=col(z))
+    ma = s1 * n
+    o["c2"] = col((z - ma) ** 2)
+    o["inv_a"] = 1.0 / torch.sqrt(s2 * n + e)
+    o["zt_a"] = (z - ma) * o["inv_a"]
+    g1, g2 = col(dzt), col(dzt * zt)
+    o["cs"] = torch.cat([g1, g2])
+    o["dz"] = (dzt - g1 / fB - zt * (g2 / fB)) * inv
+    C = z.shape[1]
+    o["dz_a"] = (dzt - sums[:C] * n - zt * (sums[C:] * n)) * (inv * torch.tensor(scale, dtype=torch.float32))
+    return o
+
+
+@functools.lru_cache(maxsize=None)
+def lfd_cm(D):
+    """Cm [D, D] f32: off-diagonals randn times 2^-8 .. 2^2 per element, the diagonal 0.7 + 0.1 randn with every third
+    entry exactly 1."""
+    gen = _gen(8400, D)
+    Cm = torch.randn(D, D, generator=gen) * torch.pow(2.0, torch.randint(-8, 3, (D, D), generator=gen).float())
+    dg = 0.7 + 0.1 * torch.randn(D, generator=gen)
+    dg[0::3] = 1.0
+    Cm.diagonal().copy_(dg)
+    return Cm
+
+
+def lfd_loss_ref64(Cm, lam, *, mut=None, aligned=True):
+    """loss = lam sum_all C^2 + sum_j ((1 - c_jj)^2 - lam c_jj^2) on the fp32 lam; scale lam sum C^2 + sum_j |(1 - c)^2 -
+    lam c^2|."""
+    l = float(np.float32(lam))
+    Cd = Cm.double()
+    c = Cd.diagonal()
+    sq = (Cd * Cd).sum()
+    if mut == "tail" and aligned:
+        n = Cd.numel()
+        sq = (Cd.reshape(-1)[:(n >> 2) << 2] ** 2).sum()
+    dterm = (1.0 - c) ** 2 - (0.0 if mut == "diag_lam" else l * c * c)
+    u = l * (Cd * Cd).sum() + dterm.abs().sum()
+    return Ref(loss=l * sq + dterm.sum(), u=u, b=NORM_C["lfd_loss"] * U24 * u)
+
+
+def lfd_dloss_ref64(Cm, g, lam, *, mut=None):
+    """dC = g (-2 (1 - c)) on the diagonal, g 2 lam c off it, within 3 u |dC| (1 - c, the product with c or with g, the
+    other product), then the bf16 rounding."""
+    l = float(np.float32(lam))
+    D = Cm.shape[0]
+    Cd = Cm.double()
+    e = torch.arange(D * D)
+    Dm = (D & ~1) if mut == "jk" and D > 1 else D
+    j = e // Dm
+    diag = ((e - j * Dm) == j).view(D, D)
+    dC = float(g) * torch.where(diag, -2.0 * (1.0 - Cd), 2.0 * l * Cd)
+    b = 3.0 * U24 * dC.abs()
+    return Ref(dC=dC, b=b, b_bf=bf16_round_bound(dC, b))
+
+
+def lfd_loss_emulate(Cm, lam, aligned=True):
+    """lfd_loss_kernel in fp32: thread t's float4s t, t + 1024, ... into two accumulators, the scalar tail, its diagonal
+    terms, lam sq + dg; the 16 waves' trees, then the waves in order."""
+    D = Cm.shape[0]
+    n = D * D
+    flat = Cm.reshape(-1)
+    l = torch.tensor(lam, dtype=torch.float32)
+    sq = torch.zeros(1024)
+    i0 = 0
+    if aligned:
+        n4 = n >> 2
+        K = (n4 + 1023) // 1024
+        p = torch.zeros(K * 1024, 4)
+        p[:n4] = flat[:n4 * 4].view(n4, 4)
+        p = p.view(K, 1024, 4)
+        a0 = _seq((p[..., 0] * p[..., 0] + p[..., 1] * p[..., 1]).permute(1, 0))
+        a1 = _seq((p[..., 2] * p[..., 2] + p[..., 3] * p[..., 3]).permute(1, 0))
+        sq = a0 + a1
+        i0 = n4 << 2
+    tail = flat[i0:]
+    K = (tail.numel() + 1023) // 1024
+    if K:
+        p = torch.zeros(K * 1024)
+        p[:tail.numel()] = tail
+        for k in range(K):
+            sq = sq + p[k * 1024:(k + 1) * 1024] ** 2
+    c = Cm.diagonal()
+    K = (D + 1023) // 1024
+    p = torch.zeros(K * 1024)
+    p[:D] = (1.0 - c) * (1.0 - c) - l * c * c
+    dg = _seq(p.view(K, 1024).permute(1, 0))
+    return _seq(_tree64((l * sq + dg).view(16, 64)))

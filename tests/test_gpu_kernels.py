@@ -727,7 +727,8 @@ def test_layernorm_fwd_bwd(film, L, fold):
     """L=32: FiLM rows fall in whole 32-row slabs -> the fused single-pass backward; L=20 with FiLM -> two
     passes (row kernel + column-slab parameter kernel). fold: dgamma / dbeta as slab sums added by one ln_fold
     launch (the decoder block's path; the two-pass form zeroes the partials and adds with atomics), on top of
-    nonzero destinations (the fold accumulates, as the atomics do)."""
+    nonzero destinations (the fold accumulates, as the atomics do). Per-element bounds of these kernels:
+    tests/test_gpu_norm_lfd_elem.py."""
     o = ops()
     B, d = 3, 192
     N = B * L

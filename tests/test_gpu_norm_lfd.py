@@ -5,6 +5,8 @@ inputs after their rounding to the storage dtype. Shapes are the smallest that r
 Tolerances: f32 outputs within 1e-5 (forward) / 1e-4 (gradients) of the largest reference magnitude, the bars of
 test_gpu_kernels.py; a bf16 output within its own rounding (2^-8 relative per element) plus the f32 bar; the file-wide
 bf16 bar TOL for a whole bf16 pipeline (L_fd end to end); dropout masks and the bf16 copy of an f32 output bit-exact.
+The per-element bars of these kernels (rounding-derived bounds on rows with offsets, outliers and zero variance, every
+build) are in tests/test_gpu_norm_lfd_elem.py and DESIGN §4.14; this file keeps the train step's shapes.
 """
 import functools
 from types import SimpleNamespace
