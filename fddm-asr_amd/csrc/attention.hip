@@ -14,6 +14,9 @@
 //                    from a [key][d] LDS image through ds_read_b64_tr_b16 (hardware transpose).
 // Work split: 4 waves x 16 rows = 64 rows per workgroup; K/V (or Q/dO) tiles of 64 rows in LDS.
 // T = bf16 (mfma_f32_16x16x32_bf16) or f32 (mfma_f32_16x16x4f32, exact fp32 parity mode).
+// The bf16 forward kernels of this file (fwd2, fwd5, fwd6) give every wave two 16-query groups and share one tile
+// body (scores2, softmax_tile, pv2, finish_group); each kernel adds only its way of bringing K / V tiles into LDS and
+// its source of bias, mask row and dropout keep words.
 #include "attn_common.h"
 
 namespace fddm {
@@ -129,33 +132,6 @@ __device__ __forceinline__ void trans_times_vals(f32x4_t (&out)[4], const unsign
   }
 }
 
-// Diagnostic build only (-DATTN_STAMPS, tools/attn_stamps.py): s_memtime stamps of wave 0 of every workgroup at the
-// phase boundaries of the v3 kernels (slot 0 entry, 1 loads issued, 2 data landed + barrier, 3.. after each key /
-// query tile, 12 stores issued, 13 exit), s_memrealtime at entry / exit (slots 14, 15) for the clock. The stamps go
-// to a buffer of their own; in the real build no stamp executes.
-#ifdef ATTN_STAMPS
-__device__ unsigned long long attn_stamps[8192 * 16];
-#define ASTAMP(k)                                                                              \
-  do {                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    unsigned long long t_;                                                                     \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    const int bl_ = blockIdx.x + blockIdx.y * gridDim.x;                                       \
-    if (threadIdx.x == 0 && bl_ < 8192) attn_stamps[bl_ * 16 + (k)] = t_;                       \
-  } while (0)
-#define ARTIME(k)                                                                              \
-  do {                                                                                         \
-    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                            \
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                                        \
-    const int bl_ = blockIdx.x + blockIdx.y * gridDim.x;                                       \
-    if (threadIdx.x == 0 && bl_ < 8192) attn_stamps[bl_ * 16 + (k)] = t_;                       \
-  } while (0)
-#else
-#define ASTAMP(k)
-#define ARTIME(k)
-#endif
-
 // Attention-probability dropout: RNG contract v2 (oracle/fddm_oracle.py: attn_dropout_keep). Per (b, h) three
 // tables of R = 4096 16-bit words, T_tau[j] = bits 16*(j&3).. of mix64(seed, stream, TAB0 + (bh*3 + tau)*1024 +
 // (j>>2)); per query row r = bh*Lq + q three offsets o_tau = (mix64(seed, stream, OFF0 + r) >> 16*tau) & 0xFFC;
@@ -268,57 +244,224 @@ __global__ void __launch_bounds__(256) fwd_kernel(AttnArgs a) {
   if (a.lse && g == 0) a.lse[(long)bh * a.Lq + q] = (l > 0.f) ? m + __logf(l) : NAN;
 }
 
-// ------------------------------------------------------------------------------------ fwd (bf16)
-// 128 queries per workgroup: each wave owns two 16-query groups, so every K fragment (LDS row read) and
-// every V^T fragment (tr read) feeds two MFMAs. K/V tiles are double-buffered in LDS; the next tile's
-// global loads are issued before this tile's MFMAs and written after them (one barrier per tile).
-// The WavLM bias slice for the tile (191 table entries: key - q spans [k0-q0-127, k0+63-q0]) is staged
-// with the tile instead of gathered from global memory per score.
-// Template flags: DROP (dropout on P), MASK (key-padding mask and/or a ragged last tile: a 0/-inf bias row
-// per tile in LDS), REL (WavLM gated relative-position bias).
-#ifndef ATTN_FWD_WPS
-#define ATTN_FWD_WPS 2  // waves per SIMD the register allocation targets (measured: 2 beats 1, 3-4 spill)
-#endif
-template <bool DROP, bool MASK, bool REL, int NG = 2>
-__global__ void __launch_bounds__(256, ATTN_FWD_WPS) fwd2_kernel(AttnArgs a) {
+// ------------------------------------------------------------------- fwd (bf16): the two-group tile body
+// fwd2, fwd5 and fwd6 share one work split and one tile body: 128 queries per workgroup, each of the 4 waves owns two
+// 16-query groups, so every K fragment (LDS row read) and every V^T fragment (tr read) feeds two MFMAs. The functions
+// below are that tile body, the two-group siblings of rows_times_frag / trans_times_vals; a kernel keeps only how a
+// K / V tile reaches LDS and where its bias, mask row and keep words come from.
+// The lane indices (g, i, w, lane) come by reference, as the tile lambdas these functions replace captured them: hipcc
+// then simplifies the index arithmetic once, after inlining and together with the kernel's own, and the generated code
+// stays that of the hand-inlined bodies (by value it folds lane >> 4 and friends early and schedules differently).
+
+// s[gq][kb] = K (KC image rows kb*16..+15) x Q^T (the fragments of query group gq)
+__device__ __forceinline__ void scores2(f32x4_t (&s)[2][4], const unsigned char* kimg, const uint4 (&qf)[2][2],
+                                        const int& g, const int& i) {
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb) {
+#pragma unroll
+    for (int gq = 0; gq < 2; ++gq) s[gq][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+      const uint4 af = *(const uint4*)(kimg + kc_off(128, kb * 16 + i, sub * 4 + g));
+#pragma unroll
+      for (int gq = 0; gq < 2; ++gq) mma<bf16_t>(s[gq][kb], af, qf[gq][sub]);
+    }
+  }
+}
+
+// the lane's 16 entries of a tile's 0 / -inf mask row (64 floats at row + k0), read once for both query groups
+__device__ __forceinline__ void mask_row(f32x2_t (&mr)[4][2], const float* row, int k0, const int& g) {
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb) {
+    const float4 mv4 = *(const float4*)(&row[k0 + kb * 16 + 4 * g]);
+    mr[kb][0] = f32x2_t{mv4.x, mv4.y};
+    mr[kb][1] = f32x2_t{mv4.z, mv4.w};
+  }
+}
+
+// Online softmax of one query group over one 64-key tile: p = the lane's 16 probabilities, m / l / o the group's
+// running max, row sum and output. Scores stay in raw units x = s (+ graw * bias[key], graw = gate / scale) (+ the
+// tile's 0 / -inf mask row mr, see mask_row); the running max m is in raw units and p = 2^(x*sl2 - m*sl2) is one
+// FMA + v_exp_f32 per score. Score pairs are carried as float2 so the bias FMA, the mask add, the exponent FMA and the
+// row sum issue as packed v_pk_* f32 instructions. MT tiles add the mask row (0 where keys are valid): a per-score
+// condition compiled to an add plus a select per score.
+// Lazy rescale (defer-max): m moves only when the tile's max exceeds it by more than th_raw = 8 / sl2 (8 in log2
+// units), decided per wave; otherwise p <= 2^8 and o, l keep their scale (no alpha exp, no O multiply on most
+// tiles). The softmax result is unchanged; only rounding differs.
+// DROP: the (query, tile) keep word comes as its halves, bit kk of keep_lo keeps key kk and of keep_hi key 32 + kk
+// (the lane uses its own 16 bits), applied as an all-ones / zero AND mask (v_bfe_i32) after the row sum; the dropout
+// scale 1/(1-p) is applied to O once in finish_group, not per kept probability.
+template <bool MT, bool BIAS, bool DROP>
+__device__ __forceinline__ void softmax_tile(float (&p)[4][4], const f32x4_t (&s)[4], const f32x2_t (&mr)[4][2],
+                                             const float* bias, int boff, float graw, unsigned keep_lo,
+                                             unsigned keep_hi, float& m, float& l, f32x4_t (&o)[4], float sl2,
+                                             float th_raw, const int& g) {
+  float tmax = -INFINITY;
+  const f32x2_t gr2 = {graw, graw};
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb) {
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      f32x2_t x = {s[kb][2 * jj], s[kb][2 * jj + 1]};
+      if constexpr (BIAS) {
+        const int kl = kb * 16 + 4 * g + 2 * jj + boff;
+        x = gr2 * f32x2_t{bias[kl], bias[kl + 1]} + x;
+      }
+      if constexpr (MT) x += mr[kb][jj];
+      p[kb][2 * jj] = x.x;
+      p[kb][2 * jj + 1] = x.y;
+    }
+    tmax = fmaxf(tmax, fmaxf(fmaxf(p[kb][0], p[kb][1]), fmaxf(p[kb][2], p[kb][3])));
+  }
+  tmax = xmax16(tmax);
+  tmax = xmax32(tmax);
+  if (__any(tmax > m + th_raw)) {  // wave-uniform: rescale O and l to the new running max
+    const float mn = fmaxf(m, tmax);
+    const float mref = (mn == -INFINITY) ? 0.f : mn;
+    const float alpha = __builtin_amdgcn_exp2f((m - mref) * sl2);
+    l *= alpha;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[d] *= alpha;
+    m = mn;
+  }
+  const float mref = (m == -INFINITY) ? 0.f : m;  // all-masked so far: exp2(-inf) = 0
+  const float nbias = -mref * sl2;
+  const f32x2_t sl2v = {sl2, sl2}, nb2 = {nbias, nbias};
+  f32x2_t ls2 = {0.f, 0.f};
+  const unsigned kwh[2] = {keep_lo, keep_hi};
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb) {
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const f32x2_t arg = f32x2_t{p[kb][2 * jj], p[kb][2 * jj + 1]} * sl2v + nb2;
+      f32x2_t e = {__builtin_amdgcn_exp2f(arg.x), __builtin_amdgcn_exp2f(arg.y)};
+      ls2 += e;
+      if constexpr (DROP) {
+        const unsigned hw = kwh[kb >> 1];
+        const int pos = (kb & 1) * 16 + 4 * g + 2 * jj;
+        const unsigned m0 = (unsigned)__builtin_amdgcn_sbfe((int)hw, pos, 1);
+        const unsigned m1 = (unsigned)__builtin_amdgcn_sbfe((int)hw, pos + 1, 1);
+        e.x = __uint_as_float(__float_as_uint(e.x) & m0);
+        e.y = __uint_as_float(__float_as_uint(e.y) & m1);
+      }
+      p[kb][2 * jj] = e.x;
+      p[kb][2 * jj + 1] = e.y;
+    }
+  }
+  l += ls2.x + ls2.y;
+}
+
+// The 4 lanes of a query hold disjoint key nibbles of its keep word for a tile: OR them, the owner lane (lane group 0
+// of a valid query) stores the 64-bit word for the backward.
+__device__ __forceinline__ void record_keep_word(uint64_t* dst, uint64_t kw, bool owner) {
+  unsigned lo = (unsigned)kw, hi = (unsigned)(kw >> 32);
+  lo = xor16(lo);
+  hi = xor16(hi);
+  lo = xor32(lo);
+  hi = xor32(hi);
+  if (owner) *dst = ((uint64_t)hi << 32) | lo;
+}
+
+// O^T += V^T P^T for both query groups: one tr-read A fragment of the V image feeds two MFMAs (the product
+// trans_times_vals2 does for the 2-group backward kernels, which keep their own copy and so their code)
+__device__ __forceinline__ void pv2(f32x4_t (&out)[2][4], const unsigned char* img, const float (&v)[2][4][4],
+                                    const int& g, const int& i) {
+  const int qq = i >> 2, pp = i & 3;
+  typedef __attribute__((address_space(3))) s16x4_t* lp;
+#pragma unroll
+  for (int ss = 0; ss < 2; ++ss) {
+    uint4 bq[2];
+#pragma unroll
+    for (int gq = 0; gq < 2; ++gq) {
+      bq[gq].x = pk(v[gq][2 * ss][0], v[gq][2 * ss][1]);
+      bq[gq].y = pk(v[gq][2 * ss][2], v[gq][2 * ss][3]);
+      bq[gq].z = pk(v[gq][2 * ss + 1][0], v[gq][2 * ss + 1][1]);
+      bq[gq].w = pk(v[gq][2 * ss + 1][2], v[gq][2 * ss + 1][3]);
+    }
+    const int k1 = 32 * ss + 4 * g + qq, k2 = k1 + 16;
+#pragma unroll
+    for (int db = 0; db < 4; ++db) {
+      const int u = db * 4 + pp;
+      const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(img + k1 * 128 + ((u ^ hatt(k1)) << 3)));
+      const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(img + k2 * 128 + ((u ^ hatt(k2)) << 3)));
+      const uint4 af = join_tr(lo, hi);
+      mma<bf16_t>(out[0][db], af, bq[0]);
+      mma<bf16_t>(out[1][db], af, bq[1]);
+    }
+  }
+}
+
+// Epilogue of one query group: row sum across the query's 4 lanes, O = o / l (times the dropout scale of the kept
+// probabilities under DROP; a fully masked row -> NaN like softmax(all -inf)) and the LSE in natural-log units.
+template <bool DROP>
+__device__ __forceinline__ void finish_group(const AttnArgs& a, int b, int h, int bh, int q, bool qv, float m, float l,
+                                             const f32x4_t (&o)[4], float sl2, int g) {
+  float lt = l;
+  lt = xsum16(lt);
+  lt = xsum32(lt);
+  if (!qv) return;
+  const float inv = (lt > 0.f) ? (DROP ? a.drop_scale : 1.f) / lt : NAN;
+  bf16_t* Ob = (bf16_t*)a.Out + ((long)b * a.Lq + q) * a.so + h * DH;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    uint2 u2;
+    u2.x = pk(o[d][0] * inv, o[d][1] * inv);
+    u2.y = pk(o[d][2] * inv, o[d][3] * inv);
+    *(uint2*)(Ob + d * 16 + 4 * g) = u2;
+  }
+  if (a.lse && g == 0) a.lse[(long)bh * a.Lq + q] = (lt > 0.f) ? (m * sl2 + __log2f(lt)) * 0.69314718055994531f : NAN;
+}
+
+// K / V stream of the ring kernels: wave w fills rows 16w .. 16w+15 of key tile tt into stage st of the rings kst (KC
+// images) and vst (tr-read images) by LDS-DMA: 2 K + 2 V instructions per wave, the XOR swizzles on the per-lane
+// source addresses; rows past the end re-read the last key (the tile's mask row masks them).
+__device__ __forceinline__ void ring_fill(const AttnArgs& a, const bf16_t* Kb, const bf16_t* Vb, unsigned char* kst,
+                                          unsigned char* vst, int tt, int st, const int& w, const int& lane) {
+  constexpr int TB = 64 * 128;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int R = 16 * w + 8 * u;
+    const int r = 64 * tt + R + (lane >> 3), pch = lane & 7;
+    const int rr = min(r, a.Lk - 1);
+    const int ck = pch ^ ((r >> 1) & 7), cv = pch ^ (((r >> 1) & 3) << 1);
+    dma16_asm(Kb + (long)rr * a.sk + ck * 8, kst + st * TB + R * 128);
+    dma16_asm(Vb + (long)rr * a.sv + cv * 8, vst + st * TB + R * 128);
+  }
+}
+
+// ------------------------------------------------------------------------------- fwd (bf16, register-staged)
+// The two-group tile body with K/V tiles double-buffered in LDS through registers: the next tile's global loads are
+// issued before this tile's MFMAs and written after them (one barrier per tile). The dropout keep bits are drawn in
+// the generic contract form (attn_keep4: 4 hashes per 4 keys; fwd6 reads precomputed words or stages the tables).
+// Template flags: DROP (dropout on P), MASK (key-padding mask and/or a ragged last tile: a 0/-inf mask row per tile
+// in LDS).
+constexpr int FWD2_WPS = 2;  // waves per SIMD the register allocation targets (measured: 2 beats 1, 3-4 spill)
+template <bool DROP, bool MASK>
+__global__ void __launch_bounds__(256, FWD2_WPS) fwd2_kernel(AttnArgs a) {
   constexpr int RB = 128;
   __shared__ __attribute__((aligned(16))) unsigned char kbuf[2][64 * RB];
   __shared__ __attribute__((aligned(16))) unsigned char vbuf[2][64 * RB];
-  __shared__ float tbuf[2][192];
   __shared__ __attribute__((aligned(16))) float mbuf[2][64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, i = lane & 15;
   int bxi, bh;
   xcd_tile(bxi, bh);
   const int b = bh / a.H, h = bh % a.H;
-  const int qbase = bxi * (64 * NG);
+  const int qbase = bxi * 128;
   const bf16_t* Qb = (const bf16_t*)a.Q + (long)b * a.Lq * a.sq + h * DH;
   const bf16_t* Kb = (const bf16_t*)a.K + (long)b * a.Lk * a.sk + h * DH;
   const bf16_t* Vb = (const bf16_t*)a.V + (long)b * a.Lk * a.sv + h * DH;
-  const float* tabh = REL ? a.table + (long)h * (2 * a.Lk - 1) : nullptr;
-  int q[NG];
-  bool qv[NG];
-  uint4 qf[NG][2];
-  float gate[NG];
+  int q[2];
+  bool qv[2];
+  uint4 qf[2][2];
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
-    q[gq] = qbase + w * (16 * NG) + gq * 16 + i;
+  for (int gq = 0; gq < 2; ++gq) {
+    q[gq] = qbase + w * 32 + gq * 16 + i;
     qv[gq] = q[gq] < a.Lq;
     row_frags<bf16_t>(qf[gq], Qb, a.sq, qv[gq] ? q[gq] : 0, qv[gq], lane);
-    gate[gq] = (a.gate && qv[gq]) ? a.gate[(long)bh * a.Lq + q[gq]] : 0.f;
-    if (REL && a.graw && qv[gq]) {
-      // gate from the 8 pre-activations the Q|K|V projection appended (HF modeling_wavlm.py:177-186)
-      const uint4 u = *(const uint4*)((const bf16_t*)a.graw + ((long)b * a.Lq + q[gq]) * a.sgr + h * 8);
-      const float ra = bf2f((bf16_t)(u.x & 0xffff)) + bf2f((bf16_t)(u.x >> 16)) + bf2f((bf16_t)(u.y & 0xffff)) +
-                       bf2f((bf16_t)(u.y >> 16));
-      const float rb = bf2f((bf16_t)(u.z & 0xffff)) + bf2f((bf16_t)(u.z >> 16)) + bf2f((bf16_t)(u.w & 0xffff)) +
-                       bf2f((bf16_t)(u.w >> 16));
-      const float ga = 1.f / (1.f + __expf(-ra)), gb = 1.f / (1.f + __expf(-rb));
-      gate[gq] = ga * (gb * a.gconst[h] - 1.f) + 2.f;
-    }
   }
   // tile loader: 512 16-B chunks of K and of V per tile, 2 each per thread
   uint4 kr[2], vr[2];
-  float tv = 0.f, mv = 0.f;
+  float mv = 0.f;
   auto load = [&](int k0) {
     const int nv = min(64, a.Lk - k0);
 #pragma unroll
@@ -329,10 +472,6 @@ __global__ void __launch_bounds__(256, ATTN_FWD_WPS) fwd2_kernel(AttnArgs a) {
         kr[u] = *(const uint4*)(Kb + (long)(k0 + r) * a.sk + c * 8);
         vr[u] = *(const uint4*)(Vb + (long)(k0 + r) * a.sv + c * 8);
       }
-    }
-    if (REL && tid < 191) {
-      const long ti = (long)k0 - qbase - 127 + (a.Lk - 1) + tid;
-      tv = (ti >= 0 && ti < 2L * a.Lk - 1) ? tabh[ti] : 0.f;
     }
     if (MASK && tid >= 192) {
       const int key = k0 + tid - 192;
@@ -346,18 +485,15 @@ __global__ void __launch_bounds__(256, ATTN_FWD_WPS) fwd2_kernel(AttnArgs a) {
       *(uint4*)(kbuf[buf] + kc_off(RB, r, c)) = kr[u];
       *(uint4*)(vbuf[buf] + r * 128 + (((2 * c) ^ hatt(r)) << 3)) = vr[u];
     }
-    if (REL && tid < 191) tbuf[buf][tid] = tv;
     if (MASK && tid >= 192) mbuf[buf][tid - 192] = mv;
   };
 
-  const float sl2 = a.scale * 1.4426950408889634f;  // running max m is kept in log2 units
-  float graw[NG];  // bias multiplier in raw score units (gate / scale), once per query instead of per tile
+  const float sl2 = a.scale * 1.4426950408889634f;  // the running max m is kept in raw score units (softmax_tile)
+  const float th_raw = 8.f / sl2;                   // lazy rescale threshold
+  float m[2], l[2];
+  f32x4_t o[2][4];
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) graw[gq] = REL ? gate[gq] / a.scale : 0.f;
-  float m[NG], l[NG];
-  f32x4_t o[NG][4];
-#pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
+  for (int gq = 0; gq < 2; ++gq) {
     m[gq] = -INFINITY;
     l[gq] = 0.f;
 #pragma unroll
@@ -368,140 +504,29 @@ __global__ void __launch_bounds__(256, ATTN_FWD_WPS) fwd2_kernel(AttnArgs a) {
   store(0);
   __syncthreads();
   const int ntiles = (a.Lk + 63) / 64;
-  // lazy rescale (defer-max): a row's running max m moves only when a tile's max exceeds it by more than 8 in
-  // log2 units, decided per wave; otherwise p = 2^(x*sl2 - m*sl2) <= 2^8 and O, l keep their scale (no alpha
-  // exp, no O multiply on most tiles). The softmax result is unchanged; only rounding differs.
-  const float th_raw = 8.f / sl2;
   auto tile = [&](const int t, auto mc) {
     constexpr bool MT = decltype(mc)::value;  // this tile adds the 0/-inf mask row
     const int cur = t & 1, k0 = t * 64;
     if (t + 1 < ntiles) load(k0 + 64);
-    const unsigned char* kimg = kbuf[cur];
-    const unsigned char* vimg = vbuf[cur];
-    f32x4_t s[NG][4];
+    f32x4_t s[2][4];
+    scores2(s, kbuf[cur], qf, g, i);
+    f32x2_t mr[4][2];
+    if constexpr (MT) mask_row(mr, mbuf[cur], 0, g);
+    float p[2][4][4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-      for (int gq = 0; gq < NG; ++gq) s[gq][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-        const uint4 af = *(const uint4*)(kimg + kc_off(RB, kb * 16 + i, sub * 4 + g));
-#pragma unroll
-        for (int gq = 0; gq < NG; ++gq) mma<bf16_t>(s[gq][kb], af, qf[gq][sub]);
-      }
-    }
-    // softmax. Scores stay in raw units x = s (+ (gate/scale)*bias) (+ the tile's 0/-inf mask row); the running
-    // max m is in raw units and p = 2^(x*sl2 - m*sl2) is one FMA + v_exp_f32 per score. Score pairs are carried
-    // as float2 so the bias FMA, the mask add, the exponent FMA and the row sum issue as packed v_pk_* f32
-    // instructions. MASK kernels add the mask row on every tile (0 where keys are valid): a per-tile condition
-    // compiled to an add plus a select per score on every tile. The dropout scale 1/(1-p) is applied to O once
-    // at the end, not per kept probability.
-    f32x2_t mrow[4][2];
-    if constexpr (MT) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        const float4 mv4 = *(const float4*)(&mbuf[cur][kb * 16 + 4 * g]);
-        mrow[kb][0] = f32x2_t{mv4.x, mv4.y};
-        mrow[kb][1] = f32x2_t{mv4.z, mv4.w};
-      }
-    }
-    float p[NG][4][4];
-#pragma unroll
-    for (int gq = 0; gq < NG; ++gq) {
-      float tmax = -INFINITY;
-      const int toff = 127 - (q[gq] - qbase);
-      const f32x2_t gr2 = {graw[gq], graw[gq]};
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-          f32x2_t x = {s[gq][kb][2 * jj], s[gq][kb][2 * jj + 1]};
-          if constexpr (REL) {
-            const int kl = kb * 16 + 4 * g + 2 * jj + toff;
-            x = gr2 * f32x2_t{tbuf[cur][kl], tbuf[cur][kl + 1]} + x;
-          }
-          if constexpr (MT) x += mrow[kb][jj];
-          p[gq][kb][2 * jj] = x.x;
-          p[gq][kb][2 * jj + 1] = x.y;
-        }
-        tmax = fmaxf(tmax, fmaxf(fmaxf(p[gq][kb][0], p[gq][kb][1]), fmaxf(p[gq][kb][2], p[gq][kb][3])));
-      }
-      tmax = xmax16(tmax);
-      tmax = xmax32(tmax);
-      if (__any(tmax > m[gq] + th_raw)) {  // wave-uniform: rescale O and l to the new running max
-        const float mn = fmaxf(m[gq], tmax);
-        const float mref = (mn == -INFINITY) ? 0.f : mn;
-        const float alpha = __builtin_amdgcn_exp2f((m[gq] - mref) * sl2);
-        l[gq] *= alpha;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) o[gq][d] *= alpha;
-        m[gq] = mn;
-      }
-      const float mref = (m[gq] == -INFINITY) ? 0.f : m[gq];  // all-masked so far: exp2(-inf) = 0
-      const float nbias = -mref * sl2;
-      const f32x2_t sl2v = {sl2, sl2}, nb2 = {nbias, nbias};
-      f32x2_t ls2 = {0.f, 0.f};
-      uint64_t bits = 0;
-      // dropout keep bits of the lane's 4 keys per block (generic contract form; fwd6 reads precomputed words)
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        unsigned keep = 0xF;
-        if constexpr (DROP) {
-          keep = attn_keep4(a, bh, q[gq], k0 + kb * 16 + 4 * g);
-          bits |= (uint64_t)keep << (kb * 16 + 4 * g);
-        }
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-          const f32x2_t arg = f32x2_t{p[gq][kb][2 * jj], p[gq][kb][2 * jj + 1]} * sl2v + nb2;
-          f32x2_t e = {__builtin_amdgcn_exp2f(arg.x), __builtin_amdgcn_exp2f(arg.y)};
-          ls2 += e;
-          if constexpr (DROP) {
-            e.x = ((keep >> (2 * jj)) & 1u) ? e.x : 0.f;
-            e.y = ((keep >> (2 * jj + 1)) & 1u) ? e.y : 0.f;
-          }
-          p[gq][kb][2 * jj] = e.x;
-          p[gq][kb][2 * jj + 1] = e.y;
-        }
-      }
-      const float ls = ls2.x + ls2.y;
+    for (int gq = 0; gq < 2; ++gq) {
+      uint64_t kw = 0;  // the lane's nibbles of the (query, tile) keep word
       if constexpr (DROP) {
-        if (a.dbits) {  // the 4 lanes of a query hold disjoint key nibbles: OR them into the tile's 64-bit word
-          unsigned lo = (unsigned)bits, hi = (unsigned)(bits >> 32);
-          lo = xor16(lo);
-          hi = xor16(hi);
-          lo = xor32(lo);
-          hi = xor32(hi);
-          if (g == 0 && qv[gq]) a.dbits[((long)bh * ntiles + t) * a.Lq + q[gq]] = ((uint64_t)hi << 32) | lo;
-        }
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+          kw |= (uint64_t)attn_keep4(a, bh, q[gq], k0 + kb * 16 + 4 * g) << (kb * 16 + 4 * g);
       }
-      l[gq] += ls;
+      softmax_tile<MT, false, DROP>(p[gq], s[gq], mr, nullptr, 0, 0.f, (unsigned)kw, (unsigned)(kw >> 32), m[gq], l[gq],
+                                    o[gq], sl2, th_raw, g);
+      if constexpr (DROP)
+        if (a.dbits) record_keep_word(&a.dbits[((long)bh * ntiles + t) * a.Lq + q[gq]], kw, g == 0 && qv[gq]);
     }
-    // O^T += V^T P^T for both query groups (one tr-read A fragment, two MFMAs)
-    {
-      const int qq = i >> 2, pp = i & 3;
-      typedef __attribute__((address_space(3))) s16x4_t* lp;
-#pragma unroll
-      for (int ss = 0; ss < 2; ++ss) {
-        uint4 bq[NG];
-#pragma unroll
-        for (int gq = 0; gq < NG; ++gq) {
-          bq[gq].x = pk(p[gq][2 * ss][0], p[gq][2 * ss][1]);
-          bq[gq].y = pk(p[gq][2 * ss][2], p[gq][2 * ss][3]);
-          bq[gq].z = pk(p[gq][2 * ss + 1][0], p[gq][2 * ss + 1][1]);
-          bq[gq].w = pk(p[gq][2 * ss + 1][2], p[gq][2 * ss + 1][3]);
-        }
-        const int k1 = 32 * ss + 4 * g + qq, k2 = k1 + 16;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          const int u = db * 4 + pp;
-          const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(vimg + k1 * 128 + ((u ^ hatt(k1)) << 3)));
-          const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(vimg + k2 * 128 + ((u ^ hatt(k2)) << 3)));
-          const uint4 af = join_tr(lo, hi);
-#pragma unroll
-          for (int gq = 0; gq < NG; ++gq) mma<bf16_t>(o[gq][db], af, bq[gq]);
-        }
-      }
-    }
+    pv2(o, vbuf[cur], p, g, i);
     if (t + 1 < ntiles) {
       store(cur ^ 1);
       __syncthreads();
@@ -515,44 +540,23 @@ __global__ void __launch_bounds__(256, ATTN_FWD_WPS) fwd2_kernel(AttnArgs a) {
     tile(ntiles - 1, std::integral_constant<bool, MASK>{});
   }
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
-    float lt = l[gq];
-    lt = xsum16(lt);
-    lt = xsum32(lt);
-    if (!qv[gq]) continue;
-    // fully masked row -> NaN like softmax(all -inf); the dropout scale of the kept probabilities goes here
-    const float inv = (lt > 0.f) ? (DROP ? a.drop_scale : 1.f) / lt : NAN;
-    bf16_t* Ob = (bf16_t*)a.Out + ((long)b * a.Lq + q[gq]) * a.so + h * DH;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      uint2 u2;
-      u2.x = pk(o[gq][d][0] * inv, o[gq][d][1] * inv);
-      u2.y = pk(o[gq][d][2] * inv, o[gq][d][3] * inv);
-      *(uint2*)(Ob + d * 16 + 4 * g) = u2;
-    }
-    if (a.lse && g == 0)
-      a.lse[(long)bh * a.Lq + q[gq]] = (lt > 0.f) ? (m[gq] * sl2 + __log2f(lt)) * 0.69314718055994531f : NAN;
-  }
+  for (int gq = 0; gq < 2; ++gq) finish_group<DROP>(a, b, h, bh, q[gq], qv[gq], m[gq], l[gq], o[gq], sl2, g);
 }
 
 // ------------------------------------------------------------------------- fwd (bf16, WavLM, streamed ring)
-// WavLM's gated relative-position attention (no dropout): fwd2's work split (4 waves x 2 query groups x 16 = 128
-// queries per workgroup) and tile body, with the K / V tiles streamed through an NST-stage LDS ring by LDS-DMA
-// (NST - 1 tiles in flight) instead of register staging (global loads, LDS writes and their address arithmetic per
-// tile, and a __syncthreads fence that drained the next tile's loads); the smaller LDS footprint lets three
-// workgroups share a CU (fwd2: two). The
+// WavLM's gated relative-position attention (no dropout): the two-group tile body with the K / V tiles streamed
+// through an NST-stage LDS ring by LDS-DMA (NST - 1 tiles in flight) instead of register staging (global loads, LDS
+// writes and their address arithmetic per tile, and a __syncthreads fence that drained the next tile's loads); the
+// smaller LDS footprint lets three workgroups share a CU (fwd2: two). The
 // bias slice of the workgroup's query range and the key mask row are staged once (as fwd6). The DMA is
 // inline asm (dma16_asm): hipcc does not track it, so it inserts no stream-draining wait before the tile's LDS
 // reads; each tile waits for its own pieces with a counted vmcnt (every wave issues exactly 4 DMA instructions per
 // tile — past the end the last tile is re-read into a free stage — and no other vector-memory instruction in the
 // loop), then a barrier; the stage of tile t-1 is refilled after it. WavLM attention 56.5 -> 52 us at C2.
-#ifndef FWD5_WPS
-#define FWD5_WPS 2  // waves per SIMD the NG = 2 build's register allocation targets (timing variants: 3, 4)
-#endif
-template <bool MASK, int NST = 2, int NG = 2>
-__global__ void __launch_bounds__(256, NG == 1 ? 4 : FWD5_WPS) fwd5_kernel(AttnArgs a) {
-  constexpr int QW = 64 * NG, TB = 64 * 128, RB = 128;
-  constexpr bool DROP = false, REL = true;
+constexpr int FWD5_WPS = 2;  // waves per SIMD the register allocation targets (timing variants: 3, 4)
+template <bool MASK>
+__global__ void __launch_bounds__(256, FWD5_WPS) fwd5_kernel(AttnArgs a) {
+  constexpr int QW = 128, TB = 64 * 128, NST = 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char sm5[];
   const int ntiles = (a.Lk + 63) / 64, LkP = ntiles * 64;
   unsigned char* kst = sm5;                      // [NST][64 rows][128 B] K, KC image
@@ -569,13 +573,13 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : FWD5_WPS) fwd5_kernel(AttnA
   const bf16_t* Kb = (const bf16_t*)a.K + (long)b * a.Lk * a.sk + h * DH;
   const bf16_t* Vb = (const bf16_t*)a.V + (long)b * a.Lk * a.sv + h * DH;
   // ---- ordinary loads first; hipcc waits for them before the stream starts (the asm below pins the registers)
-  int q[NG];
-  bool qv[NG];
-  uint4 qf[NG][2];
-  float gate[NG];
+  int q[2];
+  bool qv[2];
+  uint4 qf[2][2];
+  float gate[2];
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
-    q[gq] = qbase + w * (16 * NG) + gq * 16 + i;
+  for (int gq = 0; gq < 2; ++gq) {
+    q[gq] = qbase + w * 32 + gq * 16 + i;
     qv[gq] = q[gq] < a.Lq;
     row_frags<bf16_t>(qf[gq], Qb, a.sq, qv[gq] ? q[gq] : 0, qv[gq], lane);
     gate[gq] = (a.gate && qv[gq]) ? a.gate[(long)bh * a.Lq + q[gq]] : 0.f;
@@ -596,7 +600,7 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : FWD5_WPS) fwd5_kernel(AttnA
     const float4* wa = (const float4*)(a.gw + 16 * g);
     const float4* wb = (const float4*)(a.gw + 64 + 16 * g);
 #pragma unroll
-    for (int gq = 0; gq < NG; ++gq) {
+    for (int gq = 0; gq < 2; ++gq) {
       float sa = 0.f, sb = 0.f;
       if (qv[gq]) {
         const bf16_t* xr = (const bf16_t*)a.gx + ((long)b * a.Lq + q[gq]) * a.sgx + h * DH + 16 * g;
@@ -629,171 +633,45 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : FWD5_WPS) fwd5_kernel(AttnA
     }
   }
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
+  for (int gq = 0; gq < 2; ++gq) {
     pin16(qf[gq][0]);
     pin16(qf[gq][1]);
     asm volatile("" : "+v"(gate[gq]));
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  // ---- K / V stream: wave w fills rows 16w .. 16w+15 of a tile (2 K + 2 V instructions; XOR swizzles on the
-  // per-lane source addresses)
-  auto fill = [&](int tt, int st) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int R = 16 * w + 8 * u;
-      const int r = 64 * tt + R + (lane >> 3), pch = lane & 7;
-      const int rr = min(r, a.Lk - 1);
-      const int ck = pch ^ ((r >> 1) & 7), cv = pch ^ (((r >> 1) & 3) << 1);
-      dma16_asm(Kb + (long)rr * a.sk + ck * 8, kst + st * TB + R * 128);
-      dma16_asm(Vb + (long)rr * a.sv + cv * 8, vst + st * TB + R * 128);
-    }
-  };
+  auto fill = [&](int tt, int st) { ring_fill(a, Kb, Vb, kst, vst, tt, st, w, lane); };
 #pragma unroll
   for (int u = 0; u < NST - 1; ++u) fill(min(u, ntiles - 1), u);
 
-  const float sl2 = a.scale * 1.4426950408889634f;  // running max m is kept in log2 units
-  float graw[NG];  // bias multiplier in raw score units (gate / scale)
+  const float sl2 = a.scale * 1.4426950408889634f;  // the running max m is kept in raw score units (softmax_tile)
+  const float th_raw = 8.f / sl2;                   // lazy rescale threshold
+  float graw[2];  // bias multiplier in raw score units (gate / scale), once per query instead of per tile
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) graw[gq] = gate[gq] / a.scale;
-  float m[NG], l[NG];
-  f32x4_t o[NG][4];
+  for (int gq = 0; gq < 2; ++gq) graw[gq] = gate[gq] / a.scale;
+  float m[2], l[2];
+  f32x4_t o[2][4];
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
+  for (int gq = 0; gq < 2; ++gq) {
     m[gq] = -INFINITY;
     l[gq] = 0.f;
 #pragma unroll
     for (int d = 0; d < 4; ++d) o[gq][d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
-  const float th_raw = 8.f / sl2;  // lazy rescale threshold, as in fwd2_kernel
   auto tile = [&](const int t, auto mc) {
     constexpr bool MT = decltype(mc)::value;  // this tile adds the 0/-inf mask row
     const int k0 = t * 64;
-    const unsigned char* kimg = kst + (t % NST) * TB;
-    const unsigned char* vimg = vst + (t % NST) * TB;
-    f32x4_t s[NG][4];
+    f32x4_t s[2][4];
+    scores2(s, kst + (t % NST) * TB, qf, g, i);
+    f32x2_t mr[4][2];
+    if constexpr (MT) mask_row(mr, mfull, k0, g);
+    float p[2][4][4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-      for (int gq = 0; gq < NG; ++gq) s[gq][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-        const uint4 af = *(const uint4*)(kimg + kc_off(RB, kb * 16 + i, sub * 4 + g));
-#pragma unroll
-        for (int gq = 0; gq < NG; ++gq) mma<bf16_t>(s[gq][kb], af, qf[gq][sub]);
-      }
+    for (int gq = 0; gq < 2; ++gq) {
+      const int toff = (QW - 1) - (q[gq] - qbase) + k0;  // tfull index of (this query, the tile's first key)
+      softmax_tile<MT, true, false>(p[gq], s[gq], mr, tfull, toff, graw[gq], 0, 0, m[gq], l[gq], o[gq], sl2,
+                                    th_raw, g);
     }
-    // softmax. Scores stay in raw units x = s (+ (gate/scale)*bias) (+ the tile's 0/-inf mask row); the running
-    // max m is in raw units and p = 2^(x*sl2 - m*sl2) is one FMA + v_exp_f32 per score. Score pairs are carried
-    // as float2 so the bias FMA, the mask add, the exponent FMA and the row sum issue as packed v_pk_* f32
-    // instructions. MASK kernels add the mask row on every tile (0 where keys are valid): a per-tile condition
-    // compiled to an add plus a select per score on every tile. The dropout scale 1/(1-p) is applied to O once
-    // at the end, not per kept probability.
-    f32x2_t mrow[4][2];
-    if constexpr (MT) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        const float4 mv4 = *(const float4*)(&mfull[k0 + kb * 16 + 4 * g]);
-        mrow[kb][0] = f32x2_t{mv4.x, mv4.y};
-        mrow[kb][1] = f32x2_t{mv4.z, mv4.w};
-      }
-    }
-    float p[NG][4][4];
-#pragma unroll
-    for (int gq = 0; gq < NG; ++gq) {
-      float tmax = -INFINITY;
-      const int toff = (QW - 1) - (q[gq] - qbase) + k0;
-      const f32x2_t gr2 = {graw[gq], graw[gq]};
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-          f32x2_t x = {s[gq][kb][2 * jj], s[gq][kb][2 * jj + 1]};
-          if constexpr (REL) {
-            const int kl = kb * 16 + 4 * g + 2 * jj + toff;
-            x = gr2 * f32x2_t{tfull[kl], tfull[kl + 1]} + x;
-          }
-          if constexpr (MT) x += mrow[kb][jj];
-          p[gq][kb][2 * jj] = x.x;
-          p[gq][kb][2 * jj + 1] = x.y;
-        }
-        tmax = fmaxf(tmax, fmaxf(fmaxf(p[gq][kb][0], p[gq][kb][1]), fmaxf(p[gq][kb][2], p[gq][kb][3])));
-      }
-      tmax = xmax16(tmax);
-      tmax = xmax32(tmax);
-      if (__any(tmax > m[gq] + th_raw)) {  // wave-uniform: rescale O and l to the new running max
-        const float mn = fmaxf(m[gq], tmax);
-        const float mref = (mn == -INFINITY) ? 0.f : mn;
-        const float alpha = __builtin_amdgcn_exp2f((m[gq] - mref) * sl2);
-        l[gq] *= alpha;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) o[gq][d] *= alpha;
-        m[gq] = mn;
-      }
-      const float mref = (m[gq] == -INFINITY) ? 0.f : m[gq];  // all-masked so far: exp2(-inf) = 0
-      const float nbias = -mref * sl2;
-      const f32x2_t sl2v = {sl2, sl2}, nb2 = {nbias, nbias};
-      f32x2_t ls2 = {0.f, 0.f};
-      uint64_t bits = 0;
-      // dropout keep bits of the lane's 4 keys per block (generic contract form; fwd6 reads precomputed words)
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        unsigned keep = 0xF;
-        if constexpr (DROP) {
-          keep = attn_keep4(a, bh, q[gq], k0 + kb * 16 + 4 * g);
-          bits |= (uint64_t)keep << (kb * 16 + 4 * g);
-        }
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-          const f32x2_t arg = f32x2_t{p[gq][kb][2 * jj], p[gq][kb][2 * jj + 1]} * sl2v + nb2;
-          f32x2_t e = {__builtin_amdgcn_exp2f(arg.x), __builtin_amdgcn_exp2f(arg.y)};
-          ls2 += e;
-          if constexpr (DROP) {
-            e.x = ((keep >> (2 * jj)) & 1u) ? e.x : 0.f;
-            e.y = ((keep >> (2 * jj + 1)) & 1u) ? e.y : 0.f;
-          }
-          p[gq][kb][2 * jj] = e.x;
-          p[gq][kb][2 * jj + 1] = e.y;
-        }
-      }
-      const float ls = ls2.x + ls2.y;
-      if constexpr (DROP) {
-        if (a.dbits) {  // the 4 lanes of a query hold disjoint key nibbles: OR them into the tile's 64-bit word
-          unsigned lo = (unsigned)bits, hi = (unsigned)(bits >> 32);
-          lo = xor16(lo);
-          hi = xor16(hi);
-          lo = xor32(lo);
-          hi = xor32(hi);
-          if (g == 0 && qv[gq]) a.dbits[((long)bh * ntiles + t) * a.Lq + q[gq]] = ((uint64_t)hi << 32) | lo;
-        }
-      }
-      l[gq] += ls;
-    }
-    // O^T += V^T P^T for both query groups (one tr-read A fragment, two MFMAs)
-    {
-      const int qq = i >> 2, pp = i & 3;
-      typedef __attribute__((address_space(3))) s16x4_t* lp;
-#pragma unroll
-      for (int ss = 0; ss < 2; ++ss) {
-        uint4 bq[NG];
-#pragma unroll
-        for (int gq = 0; gq < NG; ++gq) {
-          bq[gq].x = pk(p[gq][2 * ss][0], p[gq][2 * ss][1]);
-          bq[gq].y = pk(p[gq][2 * ss][2], p[gq][2 * ss][3]);
-          bq[gq].z = pk(p[gq][2 * ss + 1][0], p[gq][2 * ss + 1][1]);
-          bq[gq].w = pk(p[gq][2 * ss + 1][2], p[gq][2 * ss + 1][3]);
-        }
-        const int k1 = 32 * ss + 4 * g + qq, k2 = k1 + 16;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          const int u = db * 4 + pp;
-          const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(vimg + k1 * 128 + ((u ^ hatt(k1)) << 3)));
-          const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(vimg + k2 * 128 + ((u ^ hatt(k2)) << 3)));
-          const uint4 af = join_tr(lo, hi);
-#pragma unroll
-          for (int gq = 0; gq < NG; ++gq) mma<bf16_t>(o[gq][db], af, bq[gq]);
-        }
-      }
-    }
+    pv2(o, vst + (t % NST) * TB, p, g, i);
   };
   auto arrive = [&](int t) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NST - 2)) : "memory");  // own pieces of tile t landed
@@ -816,23 +694,7 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : FWD5_WPS) fwd5_kernel(AttnA
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may land after the workgroup retires
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
-    float lt = l[gq];
-    lt = xsum16(lt);
-    lt = xsum32(lt);
-    if (!qv[gq]) continue;
-    const float inv = (lt > 0.f) ? 1.f / lt : NAN;  // fully masked row -> NaN like softmax(all -inf)
-    bf16_t* Ob = (bf16_t*)a.Out + ((long)b * a.Lq + q[gq]) * a.so + h * DH;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      uint2 u2;
-      u2.x = pk(o[gq][d][0] * inv, o[gq][d][1] * inv);
-      u2.y = pk(o[gq][d][2] * inv, o[gq][d][3] * inv);
-      *(uint2*)(Ob + d * 16 + 4 * g) = u2;
-    }
-    if (a.lse && g == 0)
-      a.lse[(long)bh * a.Lq + q[gq]] = (lt > 0.f) ? (m[gq] * sl2 + __log2f(lt)) * 0.69314718055994531f : NAN;
-  }
+  for (int gq = 0; gq < 2; ++gq) finish_group<false>(a, b, h, bh, q[gq], qv[gq], m[gq], l[gq], o[gq], sl2, g);
 }
 
 // ------------------------------------------------------------------ dropout keep bits (contract v2, producer)
@@ -887,20 +749,20 @@ __global__ void __launch_bounds__(256) dbits_kernel(DbArgs d) {
 
 // ---------------------------------------------------------------- fwd (bf16, decoder, streamed ring, v6)
 // The decoder's self- and cross-attention forward (key-padding mask, dropout from precomputed keep bits): fwd5's
-// streamed K / V ring (2 LDS stages filled by LDS-DMA one tile ahead, counted vmcnt + one barrier per tile) with
-// the round-2 resident-K/V forward's tile body, and the dropout keep bits read from the words dbits_kernel wrote (staged in LDS for the
+// streamed K / V ring (2 LDS stages filled by LDS-DMA one tile ahead, counted vmcnt + one barrier per tile) around the
+// two-group tile body, and the dropout keep bits read from the words dbits_kernel wrote (staged in LDS for the
 // workgroup's queries: one ds_read_b64 per tile and query instead of three table lookups, two XORs and four compares
-// per 4 keys). 4 waves x NG query groups of 16 = 64 NG queries per workgroup and 34-38 KB of LDS at Lk <= 512, so
+// per 4 keys). 4 waves x 2 query groups of 16 = 128 queries per workgroup and 34-38 KB of LDS at Lk <= 512, so
 // three to four workgroups share a CU and one workgroup's K / V loads overlap another's MFMA / softmax work (the resident forward held
 // the whole K / V range of a (b, h) in ~158 KB at Lk = 512: one workgroup per CU, 1.5 rounds of workgroups at C4).
 // Key tiles whose 64 keys are all padding are skipped (neither loaded nor computed).
 // MK: 0 no mask, 1 the ragged last tile only (Lk % 64 != 0, no key-padding mask), 2 key-padding mask on every tile.
 // DM: 0 no dropout, 1 keep bits read from words dbits_kernel wrote, 2 keep bits drawn from the contract's three
 // tables built in LDS and recorded in dbits for the backward.
-template <int DM, int MK, int NG>
-__global__ void __launch_bounds__(256, NG == 1 ? 4 : 2) fwd6_kernel(AttnArgs a) {
+template <int DM, int MK>
+__global__ void __launch_bounds__(256, 2) fwd6_kernel(AttnArgs a) {
   constexpr bool MASK = MK != 0, DROP = DM != 0;
-  constexpr int QW = 64 * NG, TB = 64 * 128, RB = 128, NST = 2;
+  constexpr int QW = 128, TB = 64 * 128, NST = 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char sm6[];
   const int ntiles = (a.Lk + 63) / 64, LkP = ntiles * 64;
   unsigned char* kst = sm6;                     // [NST][64 rows][128 B] K, KC image
@@ -918,12 +780,12 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 2) fwd6_kernel(AttnArgs a) 
   const bf16_t* Kb = (const bf16_t*)a.K + (long)b * a.Lk * a.sk + h * DH;
   const bf16_t* Vb = (const bf16_t*)a.V + (long)b * a.Lk * a.sv + h * DH;
   // ---- ordinary loads first (Q fragments, mask row, keep words); hipcc waits for them before the stream starts
-  int q[NG];
-  bool qv[NG];
-  uint4 qf[NG][2];
+  int q[2];
+  bool qv[2];
+  uint4 qf[2][2];
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
-    q[gq] = qbase + w * (16 * NG) + gq * 16 + i;
+  for (int gq = 0; gq < 2; ++gq) {
+    q[gq] = qbase + w * 32 + gq * 16 + i;
     qv[gq] = q[gq] < a.Lq;
     row_frags<bf16_t>(qf[gq], Qb, a.sq, qv[gq] ? q[gq] : 0, qv[gq], lane);
   }
@@ -935,7 +797,7 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 2) fwd6_kernel(AttnArgs a) 
       kbits[e] = (qbase + qq < a.Lq) ? src[(long)t * a.Lq + qbase + qq] : 0ull;
     }
   }
-  unsigned ooff[NG][3];  // DM 2: the rows' table offsets
+  unsigned ooff[2][3];  // DM 2: the rows' table offsets
   if constexpr (DM == 2) {
     for (int wi = tid; wi < 3 * ATTN_R / 4; wi += 256) {
       const int tau = wi / (ATTN_R / 4), jw = wi % (ATTN_R / 4);
@@ -943,7 +805,7 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 2) fwd6_kernel(AttnArgs a) 
           mix64(eff_seed(a.seed, a.seed_off), a.stream, ATTN_TAB0 + ((uint64_t)bh * 3 + tau) * (ATTN_R / 4) + jw);
     }
 #pragma unroll
-    for (int gq = 0; gq < NG; ++gq) {
+    for (int gq = 0; gq < 2; ++gq) {
       const uint64_t off = attn_offsets(a, bh, q[gq]);
 #pragma unroll
       for (int tau = 0; tau < 3; ++tau) ooff[gq][tau] = (unsigned)((off >> (16 * tau)) & 0xFFCu);
@@ -957,71 +819,40 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 2) fwd6_kernel(AttnArgs a) 
       if (__any(key_ok(a, b, 64 * t + lane))) tmask |= 1u << t;
   }
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
+  for (int gq = 0; gq < 2; ++gq) {
     pin16(qf[gq][0]);
     pin16(qf[gq][1]);
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
-  // ---- K / V stream: wave w fills rows 16w .. 16w+15 of a tile (2 K + 2 V instructions; XOR swizzles on the
-  // per-lane source addresses)
-  auto fill = [&](int tt, int st) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int R = 16 * w + 8 * u;
-      const int r = 64 * tt + R + (lane >> 3), pch = lane & 7;
-      const int rr = min(r, a.Lk - 1);
-      const int ck = pch ^ ((r >> 1) & 7), cv = pch ^ (((r >> 1) & 3) << 1);
-      dma16_asm(Kb + (long)rr * a.sk + ck * 8, kst + st * TB + R * 128);
-      dma16_asm(Vb + (long)rr * a.sv + cv * 8, vst + st * TB + R * 128);
-    }
-  };
+  auto fill = [&](int tt, int st) { ring_fill(a, Kb, Vb, kst, vst, tt, st, w, lane); };
   unsigned rem = tmask;
   int tcur = rem ? __builtin_ctz(rem) : -1;
   if (tcur >= 0) fill(tcur, 0);
 
-  const float sl2 = a.scale * 1.4426950408889634f;  // running max m is kept in raw units, p = 2^(x*sl2 - m*sl2)
-  float m[NG], l[NG];
-  f32x4_t o[NG][4];
+  const float sl2 = a.scale * 1.4426950408889634f;  // the running max m is kept in raw score units (softmax_tile)
+  const float th_raw = 8.f / sl2;                   // lazy rescale threshold
+  float m[2], l[2];
+  f32x4_t o[2][4];
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
+  for (int gq = 0; gq < 2; ++gq) {
     m[gq] = -INFINITY;
     l[gq] = 0.f;
 #pragma unroll
     for (int d = 0; d < 4; ++d) o[gq][d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
-  const float th_raw = 8.f / sl2;  // lazy rescale threshold (raw score units), as in fwd2_kernel
   auto tile = [&](const int t, const int st, auto mc) {
     constexpr bool MT = decltype(mc)::value;  // this tile adds the mask row
     const int k0 = t * 64;
-    const unsigned char* kimg = kst + st * TB;
-    const unsigned char* vimg = vst + st * TB;
-    f32x4_t s[NG][4];
+    f32x4_t s[2][4];
+    scores2(s, kst + st * TB, qf, g, i);
+    f32x2_t mr[4][2];
+    if constexpr (MT) mask_row(mr, mfull, k0, g);
+    float p[2][4][4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-      for (int gq = 0; gq < NG; ++gq) s[gq][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-        const uint4 af = *(const uint4*)(kimg + kc_off(RB, kb * 16 + i, sub * 4 + g));
-#pragma unroll
-        for (int gq = 0; gq < NG; ++gq) mma<bf16_t>(s[gq][kb], af, qf[gq][sub]);
-      }
-    }
-    f32x2_t mrow[4][2];
-    if constexpr (MT) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        const float4 mv4 = *(const float4*)(&mfull[k0 + kb * 16 + 4 * g]);
-        mrow[kb][0] = f32x2_t{mv4.x, mv4.y};
-        mrow[kb][1] = f32x2_t{mv4.z, mv4.w};
-      }
-    }
-    float p[NG][4][4];
-#pragma unroll
-    for (int gq = 0; gq < NG; ++gq) {
+    for (int gq = 0; gq < 2; ++gq) {
       uint64_t kw = 0;
-      if constexpr (DM == 1) kw = kbits[t * QW + w * (16 * NG) + gq * 16 + i];
+      if constexpr (DM == 1) kw = kbits[t * QW + w * 32 + gq * 16 + i];
       if constexpr (DM == 2) {
         // 4 x 16-bit draws per 4 keys: one aligned 8-byte word from each table, XORed
 #pragma unroll
@@ -1036,91 +867,12 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 2) fwd6_kernel(AttnArgs a) 
           kw |= (uint64_t)keep << (kb * 16 + 4 * g);
         }
       }
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-          f32x2_t x = {s[gq][kb][2 * jj], s[gq][kb][2 * jj + 1]};
-          if constexpr (MT) x += mrow[kb][jj];
-          p[gq][kb][2 * jj] = x.x;
-          p[gq][kb][2 * jj + 1] = x.y;
-        }
-        tmax = fmaxf(tmax, fmaxf(fmaxf(p[gq][kb][0], p[gq][kb][1]), fmaxf(p[gq][kb][2], p[gq][kb][3])));
-      }
-      tmax = xmax16(tmax);
-      tmax = xmax32(tmax);
-      if (__any(tmax > m[gq] + th_raw)) {
-        const float mn = fmaxf(m[gq], tmax);
-        const float mref = (mn == -INFINITY) ? 0.f : mn;
-        const float alpha = __builtin_amdgcn_exp2f((m[gq] - mref) * sl2);
-        l[gq] *= alpha;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) o[gq][d] *= alpha;
-        m[gq] = mn;
-      }
-      const float mref = (m[gq] == -INFINITY) ? 0.f : m[gq];
-      const float nbias = -mref * sl2;
-      const f32x2_t sl2v = {sl2, sl2}, nb2 = {nbias, nbias};
-      f32x2_t ls2 = {0.f, 0.f};
-      const unsigned kwh[2] = {(unsigned)kw, (unsigned)(kw >> 32)};
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-          const f32x2_t arg = f32x2_t{p[gq][kb][2 * jj], p[gq][kb][2 * jj + 1]} * sl2v + nb2;
-          f32x2_t e = {__builtin_amdgcn_exp2f(arg.x), __builtin_amdgcn_exp2f(arg.y)};
-          ls2 += e;
-          if constexpr (DROP) {
-            // keep bit of key kb*16 + 4g + 2jj (+1) as an all-ones / zero AND mask (v_bfe_i32)
-            const unsigned hw = kwh[kb >> 1];
-            const int pos = (kb & 1) * 16 + 4 * g + 2 * jj;
-            const unsigned m0 = (unsigned)__builtin_amdgcn_sbfe((int)hw, pos, 1);
-            const unsigned m1 = (unsigned)__builtin_amdgcn_sbfe((int)hw, pos + 1, 1);
-            e.x = __uint_as_float(__float_as_uint(e.x) & m0);
-            e.y = __uint_as_float(__float_as_uint(e.y) & m1);
-          }
-          p[gq][kb][2 * jj] = e.x;
-          p[gq][kb][2 * jj + 1] = e.y;
-        }
-      }
-      l[gq] += ls2.x + ls2.y;
-      if constexpr (DM == 2) {
-        if (a.dbits) {  // the 4 lanes of a query hold disjoint key nibbles: OR them into the tile's 64-bit word
-          unsigned lo = (unsigned)kw, hi = (unsigned)(kw >> 32);
-          lo = xor16(lo);
-          hi = xor16(hi);
-          lo = xor32(lo);
-          hi = xor32(hi);
-          if (g == 0 && qv[gq]) a.dbits[((long)bh * ntiles + t) * a.Lq + q[gq]] = ((uint64_t)hi << 32) | lo;
-        }
-      }
+      softmax_tile<MT, false, DROP>(p[gq], s[gq], mr, nullptr, 0, 0.f, (unsigned)kw, (unsigned)(kw >> 32), m[gq], l[gq],
+                                    o[gq], sl2, th_raw, g);
+      if constexpr (DM == 2)
+        if (a.dbits) record_keep_word(&a.dbits[((long)bh * ntiles + t) * a.Lq + q[gq]], kw, g == 0 && qv[gq]);
     }
-    {
-      const int qq = i >> 2, pp = i & 3;
-      typedef __attribute__((address_space(3))) s16x4_t* lp;
-#pragma unroll
-      for (int ss = 0; ss < 2; ++ss) {
-        uint4 bq[NG];
-#pragma unroll
-        for (int gq = 0; gq < NG; ++gq) {
-          bq[gq].x = pk(p[gq][2 * ss][0], p[gq][2 * ss][1]);
-          bq[gq].y = pk(p[gq][2 * ss][2], p[gq][2 * ss][3]);
-          bq[gq].z = pk(p[gq][2 * ss + 1][0], p[gq][2 * ss + 1][1]);
-          bq[gq].w = pk(p[gq][2 * ss + 1][2], p[gq][2 * ss + 1][3]);
-        }
-        const int k1 = 32 * ss + 4 * g + qq, k2 = k1 + 16;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          const int u = db * 4 + pp;
-          const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(vimg + k1 * 128 + ((u ^ hatt(k1)) << 3)));
-          const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(vimg + k2 * 128 + ((u ^ hatt(k2)) << 3)));
-          const uint4 af = join_tr(lo, hi);
-#pragma unroll
-          for (int gq = 0; gq < NG; ++gq) mma<bf16_t>(o[gq][db], af, bq[gq]);
-        }
-      }
-    }
+    pv2(o, vst + st * TB, p, g, i);
   };
   // one active tile per iteration: wait for its pieces (the only DMA in flight), barrier (every wave's pieces landed
   // and every wave finished the previous tile, whose stage the next fill overwrites), fill the next active tile, run
@@ -1154,23 +906,7 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 2) fwd6_kernel(AttnArgs a) 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may land after the workgroup retires
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
-    float lt = l[gq];
-    lt = xsum16(lt);
-    lt = xsum32(lt);
-    if (!qv[gq]) continue;
-    const float inv = (lt > 0.f) ? (DROP ? a.drop_scale : 1.f) / lt : NAN;
-    bf16_t* Ob = (bf16_t*)a.Out + ((long)b * a.Lq + q[gq]) * a.so + h * DH;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      uint2 u2;
-      u2.x = pk(o[gq][d][0] * inv, o[gq][d][1] * inv);
-      u2.y = pk(o[gq][d][2] * inv, o[gq][d][3] * inv);
-      *(uint2*)(Ob + d * 16 + 4 * g) = u2;
-    }
-    if (a.lse && g == 0)
-      a.lse[(long)bh * a.Lq + q[gq]] = (lt > 0.f) ? (m[gq] * sl2 + __log2f(lt)) * 0.69314718055994531f : NAN;
-  }
+  for (int gq = 0; gq < 2; ++gq) finish_group<DROP>(a, b, h, bh, q[gq], qv[gq], m[gq], l[gq], o[gq], sl2, g);
 }
 
 // ------------------------------------------------------------------------------------------- dQ
@@ -2106,8 +1842,6 @@ __global__ void __launch_bounds__(1024, 1) bwd3s_kernel(AttnArgs a) {
   float* lse_s = mfull + LP;                        // [LP] lse * log2(e), +inf past Lq
   float* del_s = lse_s + LP;                        // [LP] delta
   uint64_t* wb_s = (uint64_t*)(del_s + LP);         // [nt][LP] keep words (DM == 2)
-  ARTIME(14);
-  ASTAMP(0);
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4,
             i = lane & 15;
   int bxi, bh;
@@ -2175,10 +1909,8 @@ __global__ void __launch_bounds__(1024, 1) bwd3s_kernel(AttnArgs a) {
   if (g == 0 && q < LP) del_s[q] = qv ? delta : 0.f;
   if constexpr (DM == 2)
     if (tid < nt * LP) wb_s[tid] = wv;
-  ASTAMP(1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  ASTAMP(2);
   const f32x2_t sl2v = {sl2, sl2}, dscv = {a.drop_scale, a.drop_scale};
   typedef __attribute__((address_space(3))) s16x4_t* lp;
   // ================================================================ phase 1: dQ (query-owned, dq3's tile body)
@@ -2250,7 +1982,6 @@ __global__ void __launch_bounds__(1024, 1) bwd3s_kernel(AttnArgs a) {
           mma<bf16_t>(dq[db], join_tr(lo, hi), bq);
         }
       }
-      ASTAMP(3 + (t < 4 ? t : 4));
     };
     if (MASK && a.key_keep != nullptr) {
       for (int t = 0; t < nt; ++t)  // fully padded key tiles skipped (wave-uniform), as in fwd6_kernel
@@ -2364,7 +2095,6 @@ __global__ void __launch_bounds__(1024, 1) bwd3s_kernel(AttnArgs a) {
             mma<bf16_t>(dk[db], join_tr(qlo, qhi), bs);
           }
         }
-        ASTAMP(7 + (t < 4 ? t : 4));
       }
     }
     if (kvld) {
@@ -2383,12 +2113,6 @@ __global__ void __launch_bounds__(1024, 1) bwd3s_kernel(AttnArgs a) {
       }
     }
   }
-  ASTAMP(12);
-#ifdef ATTN_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  ASTAMP(13);
-  ARTIME(15);
 }
 
 // Kernel choice per launch shape (bf16; the fp32 parity mode runs the generic kernels):
@@ -2454,8 +2178,8 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
         if (attn7_enabled() && a.Lk <= 1024 && g_attn_v6 != 5) return attn7_fwd(a, s);
         const size_t lds5 = (size_t)2 * 2 * 64 * 128 + (size_t)LkP * 4 + (size_t)(LkP + 128) * 4;
         dim3 grid5((a.Lq + 127) / 128, a.B * a.H);
-        if (mask) hipLaunchKernelGGL((fwd5_kernel<true, 2, 2>), grid5, dim3(256), lds5, s, a);
-        else hipLaunchKernelGGL((fwd5_kernel<false, 2, 2>), grid5, dim3(256), lds5, s, a);
+        if (mask) hipLaunchKernelGGL((fwd5_kernel<true>), grid5, dim3(256), lds5, s, a);
+        else hipLaunchKernelGGL((fwd5_kernel<false>), grid5, dim3(256), lds5, s, a);
         attn_note_fwd(AF_FWD5, 0, mask, false, true);
         return (int)hipGetLastError();
       }
@@ -2483,7 +2207,7 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
                            (dm == 1 ? (size_t)ntiles * qw * 8 : dm == 2 ? (size_t)3 * ATTN_R * 2 : 0);
         dim3 g6((a.Lq + qw - 1) / qw, a.B * a.H);
         const int mk = a.key_keep != nullptr ? 2 : (a.Lk % 64) != 0 ? 1 : 0;
-#define FWD6(D, M) hipLaunchKernelGGL((fwd6_kernel<D, M, 2>), g6, dim3(256), lds, s, a)
+#define FWD6(D, M) hipLaunchKernelGGL((fwd6_kernel<D, M>), g6, dim3(256), lds, s, a)
 #define FWD6M(D) do { if (mk == 2) FWD6(D, 2); else if (mk == 1) FWD6(D, 1); else FWD6(D, 0); } while (0)
         if (dm == 2) FWD6M(2);
         else if (dm == 1) FWD6M(1);
@@ -2494,7 +2218,7 @@ static int run(int which, AttnArgs& a, hipStream_t s) {
         return (int)hipGetLastError();
       }
       dim3 grid((a.Lq + 127) / 128, a.B * a.H);
-#define FWD2(D, M) hipLaunchKernelGGL((fwd2_kernel<D, M, false>), grid, dim3(256), 0, s, a)
+#define FWD2(D, M) hipLaunchKernelGGL((fwd2_kernel<D, M>), grid, dim3(256), 0, s, a)
       if (drop) { if (mask) FWD2(true, true); else FWD2(true, false); }
       else { if (mask) FWD2(false, true); else FWD2(false, false); }
 #undef FWD2
@@ -2604,17 +2328,6 @@ static int attn_dispatch(int which, int dtype, AttnArgs& a, float drop_p, void* 
   if (dtype == FDDM_F32) return run<float>(which, a, (hipStream_t)hs);
   return (int)hipErrorInvalidValue;
 }
-
-#ifdef ATTN_STAMPS
-FDDM_API int fddm_attn_stamps(unsigned long long* host, long n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(fddm::attn::attn_stamps), n * sizeof(unsigned long long), 0,
-                                  hipMemcpyDeviceToHost);
-}
-FDDM_API int fddm_attn_stamps_clear() {
-  static unsigned long long z[8192 * 16];
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(fddm::attn::attn_stamps), z, sizeof(z), 0, hipMemcpyHostToDevice);
-}
-#endif
 
 FDDM_API int fddm_attn_last_path(void) { return (int)((unsigned)g_last_fwd | ((unsigned)g_last_bwd << 16)); }
 

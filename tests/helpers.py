@@ -936,7 +936,7 @@ def attn_bwd_units(t, q, k, v, do, o, scale):
           and no dropout has O = V, T = 0 and dQ = dK = 0 in the reference, and the kernels' T is the difference of two
           fp32 sums taken in different orders.
     Everything else is fp32 and not counted: the score MFMA accumulators, exp2, the final scalings, the f32 dQ partial
-    bwdf7 keeps in the workspace between its two key passes. dq2 / dkv2 (attention.hip :1363-1723) round at (2), (3),
+    bwdf7 keeps in the workspace between its two key passes. dq2 / dkv2 (attention.hip :1099-1459) round at (2), (3),
     (6) and (7) only: the score operand is Q itself, S s log2 e - LSE log2 e is fp32 (:1490, :1668), dK = s T^T Q
     (:1711). With e_ik^2 = T_ik^2 (1 + a_ik^2) + (2^-12 P_ik h_ik)^2:
         b_dQ[i, d] = s sqrt(sum_k e_ik^2 K_kd^2)
@@ -1538,9 +1538,9 @@ def attn_fwd_gate64(src, B, H, L, *, gate=None, graw=None, x=None, gw=None, gcon
     compute the same expression with the same __expf). Both [B, H, L].
       "gate": the precomputed fp32 row [B H, L] as given, dg = 0;
       "graw": the 4 + 4 bf16 pre-activations [B L, >= 8 H] summed, two sigmoids, ga (gb gconst[h] - 1) + 2
-              (attn7.hip :280-288, attention.hip :582-590);
+              (attn7.hip :280-288, attention.hip :586-594);
       "gx":   x [B L, >= 64 H] (bf16) against models.wavlm._fold_gate's 130 floats (attn7.hip :289-311,
-              attention.hip :593-620)."""
+              attention.hip :597-624)."""
     if src == "gate":
         g = gate.double().reshape(B, H, L)
         return g, torch.zeros_like(g)
@@ -1617,14 +1617,13 @@ def attn_fwd_units(family, r, q, k, v, scale, tripped=None):
       `tripped` [B, H, Lq] marks the rows whose wave took the fallback (attn_fwd_emulate returns it): family "7" units.
       tripped = "either" (the fwd8 guard cases) takes the larger of the two units per element instead: there the rows
       that fall back are the kernel's to decide, and tests/test_gpu_attn7.py's guard test pins which ones must.
-    family "16" (fwd6 / fwd2 / fwd5, attention.hip): Q is not pre-scaled, scores, bias and mask are fp32 (fwd2
-      :418-425, :455; fwd5 :710-715, :747; fwd6 likewise), so (1) does not exist; P o D is packed to bf16 (fwd2
-      :488-491, fwd5 :780-783, fwd6 :1107-1110), the row sum is fp32 (:457, :477), O is bf16 (:529, :829, :1167), the
-      LSE is fp32 (:534, :834, :1172):
+    family "16" (fwd6 / fwd2 / fwd5, attention.hip; the three share one tile body): Q is not pre-scaled, scores,
+      bias and mask are fp32 (softmax_tile :305-310, :336), so (1) does not exist; P o D is packed to bf16 (pv2
+      :376-379), the row sum is fp32 (:338, :351), O is bf16 (finish_group :408-409), the LSE is fp32 (:412):
           b_O^2 = sum_k P_ik^2 e_ikd^2                                      b_LSE = the fp32 terms below
-    family "f32" (fwd_kernel<float>, attention.hip :190-269): nothing rounds to bf16. u = 2^-24; the fast __expf of
-      every probability (:245) is taken as gate_out64 takes it, (|S_ik - m_i| + 4) u relative on P_ik, in numerator and
-      denominator alike; __logf (:268) is in the floor.
+    family "f32" (fwd_kernel<float>, attention.hip :166-245): nothing rounds to bf16. u = 2^-24; the fast __expf of
+      every probability (:221) is taken as gate_out64 takes it, (|S_ik - m_i| + 4) u relative on P_ik, in numerator and
+      denominator alike; __logf (:244) is in the floor.
     fp32 terms, every family (sqrt(n) 2^-24 of the root-sum-square of the n products, as attn_bwd_units (7)): the
       64-term score sums move S_ik by 8 a_ik 2^-24; the bias FMA by 2 |g_i T_ik| 2^-24 (the product and the sum); the
       Lk-term PV and row sums give sqrt(Lk) 2^-24 sqrt(sum_k P_ik^2 (e_ikd^2 + O_id^2)) on O and sqrt(Lk) 2^-24
@@ -1635,7 +1634,7 @@ def attn_fwd_units(family, r, q, k, v, scale, tripped=None):
       (4 |LSE|), exp2 / log2 / __logf are good to an ulp (8), and each of the nt rescalings of the online softmax
       multiplies the sum by an exponential of an argument of at most R_i (the f32 family's __expf: (R_i + 4) each).
     Gate term (a table was given): the kernel's gate differs from float64 by at most dg_i (attn_fwd_gate64) plus
-      2 2^-24 |g_i| for its fp32 rescaling (g log2 e, attn7.hip :313; g / s, attention.hip :356 / :657). It moves every
+      2 2^-24 |g_i| for its fp32 rescaling (g log2 e, attn7.hip :313; g / s, attention.hip :650). It moves every
       score of row i together, so it is added linearly:
           lin_O += dg_i |sum_k P_ik T_ik (e_ikd - O_id)|                   lin_LSE += dg_i |sum_k P_ik T_ik|"""
     f32 = family == "f32"
@@ -1917,8 +1916,8 @@ def attn_fwd_cases():
 
 
 # the template builds the case table must reach, as ops.attn_last_path()["fwd"] reads them (attention.hip run<>,
-# attn7.hip attn7_fwd, attn8.hip attn8_fwd). fwd2_kernel<.., REL = true> is instantiated nowhere: run<> launches fwd2
-# with REL = false only (attention.hip :2497), a table with Lk > 1024 takes fwd5.
+# attn7.hip attn7_fwd, attn8.hip attn8_fwd). fwd2_kernel has no relative-position build: a table with Lk > 1024 takes
+# fwd5.
 ATTN_FWD_BUILDS = (
     [("fwd7", dm, mk, False, False) for dm in (0, 1) for mk in (0, 1, 2)] +
     [("fwd7", dm, 2, True, False) for dm in (0, 1)] +

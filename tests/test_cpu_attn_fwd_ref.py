@@ -248,7 +248,7 @@ def test_reference_equals_float64_restatement(cid, kind):
 
 def test_case_table_reaches_every_build():
     """Every template build the dispatcher can launch, as ops.attn_last_path()["fwd"] reads it, is some case's expected
-    path (fwd2_kernel<.., REL = true> is launched by nothing: helpers.ATTN_FWD_BUILDS)."""
+    path (fwd2_kernel has no relative-position build: helpers.ATTN_FWD_BUILDS)."""
     got = {c["expect"] for c in CASES}
     missing = [b for b in ATTN_FWD_BUILDS if b not in got]
     assert not missing, missing
