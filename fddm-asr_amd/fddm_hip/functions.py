@@ -423,9 +423,11 @@ class HeadFn(torch.autograd.Function):
         ctx.bias = (bias,)
         ctx.out_ptr = logits.data_ptr()
         ctx.set_materialize_grads(False)
+        # outputs freed without a backward: swept in every precision, so that a bf16 forward that was abandoned (an
+        # evaluation pass) does not keep its KL gradient buffer alive through later fp32-mode steps
+        for k in [k for k, r in _head_outputs.items() if r() is None]:
+            _drop_handover(k)
         if xT.dtype == torch.bfloat16:
-            for k in [k for k, r in _head_outputs.items() if r() is None]:   # outputs freed without a backward
-                _drop_handover(k)
             _drop_handover(ctx.out_ptr)
             _head_outputs[ctx.out_ptr] = weakref.ref(logits)
         return logits
@@ -435,10 +437,11 @@ class HeadFn(torch.autograd.Function):
         xT, weight = ctx.saved_tensors
         dz16 = _dlogits_bf16.get(ctx.out_ptr)
         _drop_handover(ctx.out_ptr)
-        if dz16 is not None and (dlogits is None or all(st == 0 for st in dlogits.stride())):
+        if dz16 is not None and dlogits is None:
             dl = dz16                                     # the handed-over gradient, already bf16
         elif dz16 is not None:
-            dl = (dlogits + dz16.view(dlogits.shape)).to(torch.bfloat16).contiguous()  # + another consumer's part
+            # + another consumer's part, whatever its strides (c * logits.sum() sends an expanded scalar, not zeros)
+            dl = (dlogits + dz16.view(dlogits.shape)).to(torch.bfloat16).contiguous()
         elif dlogits is None:
             dl = torch.zeros(xT.shape[0], weight.shape[0], device=xT.device, dtype=xT.dtype)
         else:
@@ -479,7 +482,10 @@ class KLFn(torch.autograd.Function):
         ptr = l2.data_ptr()
         ref = _head_outputs.get(ptr)
         owner = ref() if ref is not None else None
-        bf = owner is not None and owner.data_ptr() == ptr and ptr not in _dlogits_bf16 and ptr not in _kl_dz
+        # the owner's address alone is not enough: a leading slice (logits[:1]) shares it with fewer rows, and its
+        # bf16 gradient would reach a HeadFn whose xT has all of them
+        bf = (owner is not None and owner.data_ptr() == ptr and owner.shape == l2.shape
+              and ptr not in _dlogits_bf16 and ptr not in _kl_dz)
         l2 = l2.contiguous()
         odt = torch.bfloat16 if bf else F32
         if V % 4 == 0 and V <= ops.KL_FUSED_MAX_V and l2.data_ptr() % 16 == 0:

@@ -252,14 +252,19 @@ _NO_ROPE_FUSE = os.environ.get("FDDM_ROPE_FUSE", "1") == "0"     # diagnostic A/
 def linear_dx_rope(dy2d, w, dx, cs, sn, L) -> bool:
     """dx[M,d] += rope_bwd(dy[M,n] @ w[n,d]) in one launch (fddm_linear_dx_rope: the self-attention input gradient
     through RoPE). Returns False, launching nothing, where the fused kernel does not apply (not bf16, d % 128 != 0,
-    a GEMM-family override): the caller then runs linear_dx into a temporary + rope_bwd."""
+    a GEMM-family override, or RoPE tables the kernel cannot read: cs and sn must be contiguous f32 [rows >= L, d]
+    tables of one shape on 16-byte boundaries, which the kernel reads with 16-byte loads at positions 0 .. L - 1): the
+    caller then runs linear_dx into a temporary + rope_bwd."""
     M, N = dy2d.shape
     d = w.shape[1]
     if _NO_ROPE_FUSE:
         return False
     if not (dy2d.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and dx.dtype == torch.float32 and d % 128 == 0
             and w.shape[0] == N and w.is_contiguous() and dy2d.stride(1) == 1 and dx.is_contiguous()
-            and cs.is_contiguous() and sn.is_contiguous() and cs.dtype == torch.float32 and cs.shape[-1] == d):
+            and tuple(dx.shape) == (M, d) and L > 0
+            and cs.is_contiguous() and sn.is_contiguous() and cs.dtype == torch.float32 and sn.dtype == torch.float32
+            and cs.dim() == 2 and cs.shape == sn.shape and cs.shape[-1] == d and cs.shape[0] >= L
+            and cs.data_ptr() % 16 == 0 and sn.data_ptr() % 16 == 0):
         return False
     rc = lib().fddm_linear_dx_rope(ptr(dy2d), dy2d.stride(0), ptr(w), d, ptr(dx), d, ptr(cs), ptr(sn), M, d, N, L,
                                    stream())

@@ -3499,3 +3499,374 @@ def lfd_loss_emulate(Cm, lam, aligned=True):
     p[:D] = (1.0 - c) * (1.0 - c) - l * c * c
     dg = _seq(p.view(K, 1024).permute(1, 0))
     return _seq(_tree64((l * sq + dg).view(16, 64)))
+
+
+# ------------------------------------------------ the autograd Functions (fddm_hip/functions.py)
+# Float64 restatements of what each torch.autograd.Function claims to be, as plain differentiable torch graphs, shared by
+# tests/test_cpu_functions_ref.py (references against the oracle, mutants against the bounds, balance of the loss
+# coefficients) and tests/test_gpu_functions.py (the Functions on the device). Every operand sits on the bf16 grid, so
+# the fp32 and the bf16 mode read the values the reference reads. Gradients are float64 autograd of the composite loss.
+# Each gradient comes with a magnitude companion: the same linear maps on absolute operands (as gemm_bound's s). The
+# bound per element is |got - ref| <= C u companion, u = 2^-24 (fp32 mode) or 2^-9 (bf16 mode), C = min(64, 8 E), E the
+# worst ratio |got - ref| / (u companion) measured on the MI355X over every case of the tables below, one per (Function,
+# output, precision), stored with measured <= stored <= 1.1 measured + FN_E_FLOOR. The wiring errors in question (a share
+# of the logits gradient lost, a scale ignored, overwrite for accumulate) are of the companion's own size: the CPU file
+# proves that they leave the bound at C = 64.
+# EmbedFn and CondFn compute in fp32 in both modes (csrc/small.hip, the f32 embedding): their u is 2^-24 in both.
+U9 = 2.0 ** -9
+FN_U = {"fp32": U24, "bf16": U9}
+FN_E_FLOOR = 0.05
+FN_E = {
+    # (function, gradient, precision): E, measured on an MI355X (tests/test_gpu_functions.py prints them as FNE lines);
+    # the worst case of each stands behind it.
+    # head: the HeadFn / KLFn / TextEmbedFn hand-over matrix; hw, hb = the head's weight and bias, x = its input, tw = the
+    # text weight, dl = the logits gradient (observable in fp32 mode only). The fp32 figures are what the logits' own
+    # rounding (u times ~10 |logit|-sized terms) costs through the softmax: the fp32 evaluation on the CPU shows 8 .. 21
+    ("head", "hw", "fp32"): 20.3,     # 18.46  kl_g V=301 no mask
+    ("head", "hb", "fp32"): 11.8,     # 10.76  kl_slice V=301 no mask
+    ("head", "x", "fp32"): 18.6,      # 16.92  kl_g V=301 masked
+    ("head", "tw", "fp32"): 25.9,     # 23.55  text V=301 no mask
+    ("head", "dl", "fp32"): 36.6,     # 33.26  text V=304 no mask
+    ("head", "hw", "bf16"): 5.15,     # 4.66   kl_g_text V=304 no mask
+    ("head", "hb", "bf16"): 3.78,     # 3.41   kl_g_text V=304 masked
+    ("head", "x", "bf16"): 2.75,      # 2.47   kl_g_text V=304 no mask
+    ("head", "tw", "bf16"): 1.7,      # 1.52   text V=300 no mask
+    ("linear", "x", "fp32"): 3.08,    # 2.77   out 100, weight frozen, arena
+    ("linear", "w", "fp32"): 1.7,     # 1.51   out 256, x detached, weight in the arena
+    ("linear", "b", "fp32"): 0.11,    # 0.056  out 256, weight frozen, arena
+    # bf16 mode: operands and cotangents on the bf16 grid, fp32 accumulation: nothing is rounded at 2^-9 (< 0.0005)
+    ("linear", "x", "bf16"): 0.05, ("linear", "w", "bf16"): 0.05, ("linear", "b", "bf16"): 0.05,
+    ("lfd", "za", "fp32"): 14.6,      # 13.26  g = 1
+    ("lfd", "zb", "fp32"): 10.15,     # 9.22   g = 0.37
+    ("lfd", "za", "bf16"): 5.15,      # 4.66   g = 0.37
+    ("lfd", "zb", "bf16"): 4.8,       # 4.35   g = 0.37
+    # EmbedFn / CondFn: fp32 arithmetic in both modes, the same figures in both
+    ("cond", "time", "fp32"): 6.6,    # 5.98   NL 2, d 200, mlp.2.weight
+    ("cond", "film", "fp32"): 1.55,   # 1.38   NL 2, d 200, scale_proj.weight of block 0
+    ("cond", "emb", "fp32"): 0.05,    # 0: at most three bf16-grid rows meet in one embedding row, their fp32 sum is exact
+    ("cond", "time", "bf16"): 6.6, ("cond", "film", "bf16"): 1.55, ("cond", "emb", "bf16"): 0.05,
+}
+
+
+def fn_c(fn, out, prec):
+    return min(64.0, 8.0 * FN_E[(fn, out, prec)])
+
+
+def _grid(x):
+    """x rounded onto the bf16 grid, as float32."""
+    return x.to(torch.bfloat16).float()
+
+
+def fn_excess(got, ref, comp, u):
+    """max |got - ref| / (u companion) (elements whose companion is 0 must agree exactly: inf otherwise)."""
+    err = (got.detach().double().cpu() - ref).abs()
+    assert err.shape == comp.shape, (err.shape, comp.shape)
+    pos = comp > 0
+    if (err[~pos] != 0).any():
+        return float("inf")
+    return (err[pos] / (u * comp[pos])).max().item() if pos.any() else 0.0
+
+
+# ---- HeadFn / KLFn / TextEmbedFn: the logits gradient's way from its consumers to the head
+HEAD_B, HEAD_L, HEAD_D, HEAD_T, HEAD_TW = 3, 20, 128, 10, 64     # 60 rows: no multiple of 8, 32 or 64
+HEAD_V = (304, 300, 301)       # V % 8 == 0 (the combined bf16 buffer) | V % 4 == 0 only (one-pass KL, f32 text part) |
+#                                the two-pass KL and the zero-padded GEMMs
+HEAD_G = 0.375                 # the KL's weight where it is not 1 (a GradScaler, a weighted KL)
+# loss coefficients of the text, dense and expanded consumers, balanced so that every consumer's share of the logits
+# gradient's companion has its median within 4x of the KL's (tests/test_cpu_functions_ref.py asserts it)
+HEAD_CT, HEAD_CD, HEAD_CE = 2.0 ** -13, 2.0 ** -15, 2.0 ** -15
+# name -> the consumers of the logits in the order the graph is built (autograd runs their backwards in the reverse):
+# (kind, coefficient). kl: KLFn on the whole logits; klslice: KLFn on logits[:1]; text: (TextEmbedFn(logits) * Rz).sum();
+# dense: (logits * R).sum(); expand: logits.sum(), whose gradient arrives as an expanded (zero-stride) scalar
+HEAD_CASES = {
+    "kl": (("kl", 1.0),),
+    "kl_g": (("kl", HEAD_G),),
+    "kl_text": (("kl", 1.0), ("text", HEAD_CT)),
+    "kl_g_text": (("kl", HEAD_G), ("text", HEAD_CT)),
+    "text_kl": (("text", HEAD_CT), ("kl", 1.0)),
+    "text": (("text", HEAD_CT),),
+    "kl_dense": (("kl", 1.0), ("dense", HEAD_CD)),
+    "kl_expand": (("kl", 1.0), ("expand", HEAD_CE)),
+    "kl_kl": (("kl", 1.0), ("kl", HEAD_G)),
+    "kl_slice": (("klslice", 1.0),),
+}
+HEAD_ALL = (("kl", HEAD_G), ("text", HEAD_CT), ("dense", HEAD_CD), ("expand", HEAD_CE))   # the mutants' composite
+HEAD_MUTANTS = ("no_expand", "no_dense", "kl_unscaled", "kl_twice", "no_text")
+
+
+@functools.lru_cache(maxsize=None)
+def head_inputs(V, masked):
+    """Operands of the hand-over matrix on the bf16 grid (f32 tensors): x [N, d] the head's input (randn times a power
+    of two per row), hw [V, d] and hb [V] (logits of spread ~1.5), tw [64, V] the text weight with one sign per column
+    (so that the text share of a logits column keeps its sign over the rows and shows in the bias gradient), Rz
+    [N, 64] > 0 and R [N, V] > 0 the cotangents of the text and the dense consumer; xt, x0 [B, L] (every third token
+    x0 == xt), t = (1, T, 5), x_mask [B, L] with the tail of row 1 padded (or None), the scheduler's betas."""
+    from oracle import fddm_oracle as O
+    B, L, d, Tn, TW = HEAD_B, HEAD_L, HEAD_D, HEAD_T, HEAD_TW
+    gen = _gen(9100, V)
+    N = B * L
+    x = _grid(torch.randn(N, d, generator=gen) * _pow2(gen, N, -1, 1)[:, None])
+    hw = _grid(0.11 * torch.randn(V, d, generator=gen))
+    hb = _grid(0.5 * torch.randn(V, generator=gen))
+    sign = torch.where(torch.rand(V, generator=gen) < 0.5, -1.0, 1.0)
+    tw = _grid((0.25 + torch.randn(TW, V, generator=gen).abs()) * sign[None, :] * _pow2(gen, TW, -1, 1)[:, None])
+    Rz = _grid(0.25 + torch.randn(N, TW, generator=gen).abs())
+    R = _grid(0.25 + torch.randn(N, V, generator=gen).abs())
+    x0 = torch.randint(0, V, (B, L), generator=gen)
+    xt = torch.randint(0, V, (B, L), generator=gen)
+    xt.view(-1)[::3] = x0.view(-1)[::3]
+    t = torch.tensor([1, Tn, 5])
+    mask = None
+    if masked:
+        mask = torch.ones(B, L, dtype=torch.bool)
+        mask[1, 14:] = False
+    betas, _ = O.sched_tables(Tn)
+    return Ref(x=x, hw=hw, hb=hb, tw=tw, Rz=Rz, R=R, xt=xt, x0=x0, t=t, mask=mask, betas=betas.float())
+
+
+def head_ref64(V, masked, consumers, dtype=torch.float64, mut=None):
+    """The composite loss sum_i c_i consumer_i(logits), logits = x hw^T + hb, as a plain torch graph in `dtype`, and its
+    autograd gradients: g = {x, hw, hb, tw (None without a text consumer), dl = d loss / d logits}, all float64.
+    Companions m (same keys): m_dl = the sum of the consumers' shares, KL: |c| s (kl_term_ref64's scale), text:
+    |c| xhat (a + sum_j xhat_j a_j) with a = |Rz| |tw|, dense |c R|, expand |c|; hw: m_dl^T |x|; hb: the column sums of
+    m_dl; x: m_dl |hw|; tw: |c Rz|^T xhat. shares = {kind: its part of m_dl}, terms = {kind: c_i consumer_i}.
+    mut (tests/test_cpu_functions_ref.py): no_expand / no_dense / no_text drop that consumer, kl_unscaled takes every
+    KL with weight 1, kl_twice with weight 1 + c (the unscaled share left in the buffer and the scaled one added)."""
+    i = head_inputs(V, masked)
+    B, L = HEAD_B, HEAD_L
+    x, hw, hb, tw = (v.clone().to(dtype).requires_grad_(True) for v in (i.x, i.hw, i.hb, i.tw))
+    logits = x @ hw.t() + hb
+    logits.retain_grad()
+    lg = logits.view(B, L, V)
+    loss = torch.zeros((), dtype=dtype)
+    m_dl = torch.zeros(B * L, V, dtype=torch.float64)
+    m_tw = None
+    shares, terms = {}, {}
+    for kind, c in consumers:
+        if mut == "no_" + kind:
+            continue
+        if kind in ("kl", "klslice"):
+            r = B if kind == "kl" else 1
+            cm = 1.0 if mut == "kl_unscaled" else (1.0 + c) if mut == "kl_twice" else c
+            kl_tok, _, w, s = kl_term_ref64(lg[:r], i.xt[:r], i.x0[:r], i.t[:r], None if i.mask is None else i.mask[:r],
+                                            i.betas, dtype=dtype)
+            term = cm * (w.detach() * kl_tok).sum()
+            sh = torch.zeros(B, L, V, dtype=torch.float64)
+            sh[:r] = abs(c) * s.detach().double()
+            sh = sh.view(B * L, V)
+        elif kind == "text":
+            xhat = torch.softmax(logits, -1)
+            term = c * ((xhat @ tw.t()) * i.Rz.to(dtype)).sum()
+            xh = xhat.detach().double()
+            a = (abs(c) * i.Rz.double()) @ i.tw.double().abs()
+            sh = xh * (a + (xh * a).sum(-1, keepdim=True))
+            mt = (abs(c) * i.Rz.double()).t() @ xh
+            m_tw = mt if m_tw is None else m_tw + mt
+        elif kind == "dense":
+            term = c * (logits * i.R.to(dtype)).sum()
+            sh = abs(c) * i.R.double()
+        elif kind == "expand":
+            term = c * logits.sum()
+            sh = torch.full((B * L, V), abs(c), dtype=torch.float64)
+        else:
+            raise ValueError(kind)
+        loss = loss + term
+        m_dl = m_dl + sh
+        shares[kind] = shares.get(kind, 0) + sh
+        terms[kind] = terms.get(kind, 0.0) + float(term.detach())
+    loss.backward()
+    g = {"x": x.grad, "hw": hw.grad, "hb": hb.grad, "tw": tw.grad if m_tw is not None else None, "dl": logits.grad}
+    g = {k: (None if v is None else v.detach().double()) for k, v in g.items()}
+    m = {"dl": m_dl, "hw": m_dl.t() @ i.x.double().abs(), "hb": m_dl.sum(0), "x": m_dl @ i.hw.double().abs(), "tw": m_tw}
+    return Ref(loss=float(loss.detach()), g=g, m=m, shares=shares, terms=terms)
+
+
+@functools.lru_cache(maxsize=None)
+def head_case_ref(name, V, masked):
+    return head_ref64(V, masked, HEAD_CASES[name])
+
+
+# ---- LinearFn
+# (rows shape, in, out): 45 rows as [3, 15, 128] -> 256 | out = 100 (100 % 8 = 4: the zero-padded GEMMs)
+LINEAR_SHAPES = (((3, 15), 128, 256), ((3, 15), 128, 100))
+LINEAR_NEEDS = ("all", "x_detached", "w_frozen")      # w_frozen: the bias alone trains (the colsum branch)
+LINEAR_DEST = ("fresh", "arena", "w_arena")           # w_arena: the weight in a GradArena, the bias fresh (ab != aw)
+
+
+def linear_fn_cases():
+    """(shape index, bias, needs, dest) of every LinearFn case that is not another one in disguise: no frozen weight
+    without a bias (nothing trains), no w_arena without a trainable weight and a bias."""
+    out = []
+    for si in range(len(LINEAR_SHAPES)):
+        for bias in (False, True):
+            for needs in LINEAR_NEEDS:
+                for dest in LINEAR_DEST:
+                    if needs == "w_frozen" and (not bias or dest == "w_arena"):
+                        continue
+                    if dest == "w_arena" and not bias:
+                        continue
+                    out.append((si, bias, needs, dest))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def linear_fn_inputs(si):
+    """x [3, 15, in], w [out, in], b [out] and the cotangents Ry of the two passes [2, 3, 15, out], on the bf16 grid."""
+    lead, K, N = LINEAR_SHAPES[si]
+    gen = _gen(9200, si)
+    M = lead[0] * lead[1]
+    x = _grid(torch.randn(M, K, generator=gen) * _pow2(gen, M)[:, None]).view(*lead, K)
+    w = _grid(torch.randn(N, K, generator=gen) * _pow2(gen, N)[:, None] * 0.1)
+    b = _grid(torch.randn(N, generator=gen))
+    Ry = _grid(torch.randn(2, M, N, generator=gen) * _pow2(gen, N)[None, None, :]).view(2, *lead, N)
+    return Ref(x=x, w=w, b=b, Ry=Ry)
+
+
+@functools.lru_cache(maxsize=None)
+def linear_fn_ref64(si, bias, dtype=torch.float64, mut=None):
+    """y = x w^T + b and the gradients of two forward / backward passes, loss_p = (y Ry_p).sum(), summed as .grad or a
+    grad-arena slot sums them: g = {x, w, b}, companions m = sum_p (|Ry_p| |w|, |Ry_p|^T |x|, the column sums of
+    |Ry_p|). y is returned too. mut = "b_overwrite": the second pass overwrites the bias gradient."""
+    i = linear_fn_inputs(si)
+    x, w, b = (v.clone().to(dtype).requires_grad_(True) for v in (i.x, i.w, i.b))
+    y = x @ w.t() + (b if bias else 0.0)
+    ((y * i.Ry[0].to(dtype)).sum() + (y * i.Ry[1].to(dtype)).sum()).backward()
+    g = {"x": x.grad.double(), "w": w.grad.double(), "b": b.grad.double() if bias else None}
+    if mut == "b_overwrite" and bias:
+        g["b"] = i.Ry[1].double().reshape(-1, w.shape[0]).sum(0)
+    Ra = (i.Ry[0].double().abs() + i.Ry[1].double().abs()).reshape(-1, w.shape[0])
+    xa = i.x.double().abs().reshape(-1, w.shape[1])
+    m = {"x": (Ra @ i.w.double().abs()).view(i.x.shape), "w": Ra.t() @ xa, "b": Ra.sum(0)}
+    return Ref(y=y.detach().double(), g=g, m=m)
+
+
+# ---- LfdFn
+LFD_FN = (4, 6, 64)            # B, T, D
+LFD_FN_G = (1.0, 0.37)         # the upstream scalar
+LFD_FN_LAM = 5e-3
+
+
+@functools.lru_cache(maxsize=None)
+def lfd_fn_inputs():
+    """z_a, z_b [B, T, D] on the bf16 grid. Each (t, d) column is standardised over the batch exactly and given a scale
+    0.75 .. 1.25 times a power of two and an offset, so that every column's batch standard deviation is within 0.25 of
+    the median column's (at B = 4 a raw randn column can be 100 times flatter: the standardisation would amplify its
+    rounding by that factor); z_b = 0.6 z_a's standardised column + 0.8 another, so the correlation's diagonal is ~0.6."""
+    B, Tn, D = LFD_FN
+    gen = _gen(9300, B, Tn, D)
+
+    def std(v):
+        v = v - v.mean(0, keepdim=True)
+        return v / v.pow(2).mean(0, keepdim=True).sqrt()
+
+    a = std(torch.randn(B, Tn, D, generator=gen, dtype=torch.float64))
+    n = std(torch.randn(B, Tn, D, generator=gen, dtype=torch.float64))
+    b = std(0.6 * a + 0.8 * n)
+    out = []
+    for v in (a, b):
+        sc = (0.75 + 0.5 * torch.rand(Tn, D, generator=gen, dtype=torch.float64))
+        off = torch.randn(Tn, D, generator=gen, dtype=torch.float64)
+        out.append(_grid((v * sc + off).float()))
+    return out[0], out[1]
+
+
+@functools.lru_cache(maxsize=None)
+def lfd_fn_ref64(g, dtype=torch.float64, mut=None):
+    """g * oracle.lfd_loss(z_a, z_b) in `dtype` and its autograd gradients {za, zb} (float64). No magnitude can be
+    carried through the batch standardisation (its backward subtracts two batch means): the companion of an element is
+    max |ref| over its column d (all b, t), m = {za, zb} [1, 1, D]. mut = "nt_once": 1 / (B T) applied once instead of
+    twice (the backward GEMMs' alpha left out): the gradients times B T."""
+    from oracle import fddm_oracle as O
+    B, Tn, D = LFD_FN
+    za, zb = (v.clone().to(dtype).requires_grad_(True) for v in lfd_fn_inputs())
+    loss = O.lfd_loss(za, zb, LFD_FN_LAM, LN_EPS)
+    (g * loss).backward()
+    k = float(B * Tn) if mut == "nt_once" else 1.0
+    gr = {"za": k * za.grad.double(), "zb": k * zb.grad.double()}
+    ref = gr if mut is None and dtype == torch.float64 else lfd_fn_ref64(g).g
+    m = {n: v.abs().amax((0, 1), keepdim=True).expand_as(v).contiguous() for n, v in ref.items()}
+    return Ref(loss=float(loss.detach()), g=gr, m=m)
+
+
+# ---- EmbedFn + CondFn: t_bias = time_proj(mlp(sinusoid(t))), FiLM projections of the pooled condition, x = E[xt] + t_bias
+COND_FN_B, COND_FN_L, COND_FN_V = 3, 7, 11
+COND_FN_NL = (0, 2)
+COND_FN_D = (128, 200)
+COND_FN_MODES = ("gbuf", "foreign", "film_only")   # FiLM gradients as gbuf slices | foreign tensors, one None (the
+#                                                    stacked branch) | no gradient for t_bias (dtb = None)
+
+
+@functools.lru_cache(maxsize=None)
+def cond_fn_inputs(NL, d):
+    """The conditioning path's operands on the bf16 grid: t = (1, 10, 3), pooled [B, d], the six time-path parameters,
+    2 NL FiLM (weight, bias) pairs, E [V, d] with the pad row 0 zero, xt [B, L] with pad tokens, cotangents Rx [B L, d] of
+    the embedding output and Rf [2 NL, B, d] of the FiLM outputs."""
+    B, L, V = COND_FN_B, COND_FN_L, COND_FN_V
+    gen = _gen(9400, NL, d)
+    rn = lambda *s, k=1.0: _grid(k * torch.randn(*s, generator=gen))     # noqa: E731
+    p = [rn(4 * d, d, k=0.1), rn(4 * d, k=0.5), rn(d, 4 * d, k=0.05), rn(d, k=0.5), rn(d, d, k=0.1), rn(d, k=0.5)]
+    for _ in range(2 * NL):
+        p += [rn(d, d, k=0.1), rn(d, k=0.5)]
+    E = rn(V, d)
+    E[0] = 0.0
+    xt = torch.randint(1, V, (B, L), generator=gen)
+    xt[1, 4:] = 0
+    xt[2, 2] = 0
+    return Ref(t=torch.tensor([1, 10, 3]), pooled=rn(B, d), params=tuple(p), E=E, xt=xt, Rx=rn(B * L, d),
+               Rf=rn(max(2 * NL, 1), B, d)[:2 * NL])
+
+
+@functools.lru_cache(maxsize=None)
+def cond_fn_ref64(NL, d, mode, dtype=torch.float64):
+    """loss = (x Rx).sum() + sum_i (film_i Rf_i).sum() (mode film_only: the FiLM part alone; mode foreign: FiLM output
+    1 unused), x = E[xt] + t_bias[b], t_bias = Wp (W2 silu(W1 emb + b1) + b2) + bp on the float64 time embedding
+    (te_ref64), film_i = pooled Wf_i^T + bf_i. g = {E, p0 .. p(5 + 4 NL)} (None where the loss does not reach), m the
+    companions: the backward with every operand and every intermediate cotangent replaced by its magnitude
+    (|silu'(pre)| for the activation; the embedding's magnitude is |emb| + its argument's, te_ref64's unit)."""
+    i = cond_fn_inputs(NL, d)
+    B, L = COND_FN_B, COND_FN_L
+    te = te_ref64(i.t, d)
+    emb = te.emb.to(dtype)
+    P = [v.clone().to(dtype).requires_grad_(True) for v in i.params]
+    E = i.E.clone().to(dtype).requires_grad_(True)
+    W1, b1, W2, b2, Wp, bp = P[:6]
+    pre = emb @ W1.t() + b1
+    h = torch.nn.functional.silu(pre)
+    tev = h @ W2.t() + b2
+    tb = tev @ Wp.t() + bp
+    x = torch.nn.functional.embedding(i.xt, E, padding_idx=0) + tb[:, None]
+    loss = torch.zeros((), dtype=dtype)
+    time_used = mode != "film_only"
+    if time_used:
+        loss = loss + (x.reshape(B * L, d) * i.Rx.to(dtype)).sum()
+    pooled = i.pooled.to(dtype)
+    used = [not (mode == "foreign" and k == 1) for k in range(2 * NL)]
+    for k in range(2 * NL):
+        if used[k]:
+            loss = loss + ((pooled @ P[6 + 2 * k].t() + P[7 + 2 * k]) * i.Rf[k].to(dtype)).sum()
+    if loss.requires_grad:
+        loss.backward()
+    g = {"E": E.grad}
+    for k, v in enumerate(P):
+        g[f"p{k}"] = v.grad
+    g = {k: (None if v is None else v.double()) for k, v in g.items()}
+    m = {k: None for k in g}
+    if time_used:
+        Rx = i.Rx.double().abs()
+        live = (i.xt.view(-1) != 0)
+        m["E"] = torch.zeros(COND_FN_V, d, dtype=torch.float64).index_add_(0, i.xt.view(-1)[live], Rx[live])
+        dtb = Rx.view(B, L, d).sum(1)
+        a = lambda v: v.detach().double().abs()     # noqa: E731
+        dte = dtb @ a(Wp)
+        dh = dte @ a(W2)
+        dpre = dh * dsilu64(pre.detach().double()).abs()
+        m_emb = te.emb.abs() + te.unit / U24
+        m_tev = a(h) @ a(W2).t() + a(b2)            # te's terms, not |te|: the roundings of its sum reach dWp
+        m.update(p5=dtb.sum(0), p4=dtb.t() @ m_tev, p3=dte.sum(0), p2=dte.t() @ a(h), p1=dpre.sum(0),
+                 p0=dpre.t() @ m_emb)
+    for k in range(2 * NL):
+        if used[k]:
+            Rf = i.Rf[k].double().abs()
+            m[f"p{6 + 2 * k}"] = Rf.t() @ i.pooled.double().abs()
+            m[f"p{7 + 2 * k}"] = Rf.sum(0)
+    return Ref(g=g, m=m, tb=tb.detach().double(), x=x.detach().double().reshape(B * L, d), used=used)
