@@ -7,6 +7,8 @@
 //                         one workgroup per token, the V-row held in registers (one HBM read,
 //                         one write). Closed form: SURVEY §8(a) "KL closed form".
 //  * fddm_softmax_rows / fddm_softmax_bwd_rows — TextEmbedding (models/projection.py:41-47).
+//  * fddm_*_wide        — the KL and softmax row kernels with the row streamed in chunks instead of held, for
+//                         vocabularies beyond the register-resident kernels (up to V = 2^24).
 #include "common.h"
 #include <type_traits>
 #include <cstdlib>
@@ -710,6 +712,343 @@ __global__ void __launch_bounds__(256) axpy_if_kernel(bf16_t* __restrict__ x, co
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Streamed ("wide") row kernels: the same arithmetic as the resident kernels above for vocabularies a workgroup cannot
+// hold in registers (V up to 2^24, where (float)V is still exact). One 512-thread workgroup per row walks the row in
+// chunks of WIDE_C = 8192 elements (16 per thread: four float4, or sixteen lane-strided scalars where V % 4 != 0 or a
+// row is not 16-byte aligned) and re-reads it for each further pass; consecutive passes walk in opposite directions,
+// so a pass starts on the chunk the one before it touched last (a 128 - 512 KB row comes back from L2 / MALL).
+// Chunks that lie wholly inside the row carry no bounds test; only the last, partly filled one does. Every index is
+// a long: N * V passes 2^31 at real sizes.
+constexpr int WIDE_NT = 512;                 // threads per row
+constexpr int WIDE_E = 16;                   // elements per thread and chunk
+constexpr long WIDE_C = (long)WIDE_NT * WIDE_E;  // elements per chunk
+constexpr long WIDE_MAX_V = 1L << 24;
+constexpr float WIDE_L2E = 1.4426950408889634f;
+
+// row index of this thread's element e (0..15) in the chunk starting at `base`: float4 u = e / 4 of the thread sits at
+// float4 tid + 512 u of the chunk (vector form); element e at tid + 512 e (scalar form)
+template <bool VEC>
+__device__ __forceinline__ long wide_k(long base, int tid, int e) {
+  if constexpr (VEC) return base + 4L * (tid + WIDE_NT * (e >> 2)) + (e & 3);
+  else return base + tid + (long)WIDE_NT * e;
+}
+// v[e] = p[wide_k(e)] as float, `fill` past the row's end (TAIL chunks only). Vector form: 16-B (f32) or 8-B (bf16)
+// loads; V % 4 == 0 there, so a float4 is inside the row or outside it as a whole.
+template <typename T, bool VEC, bool TAIL>
+__device__ __forceinline__ void wide_ld(const T* p, long base, long V, int tid, float (&v)[WIDE_E], float fill) {
+  if constexpr (VEC) {
+#pragma unroll
+    for (int u = 0; u < WIDE_E / 4; ++u) {
+      const long k0 = wide_k<true>(base, tid, 4 * u);
+      if (TAIL && k0 >= V) {
+        v[4 * u] = v[4 * u + 1] = v[4 * u + 2] = v[4 * u + 3] = fill;
+      } else if constexpr (sizeof(T) == 4) {
+        const float4 f = *(const float4*)(p + k0);
+        v[4 * u] = f.x; v[4 * u + 1] = f.y; v[4 * u + 2] = f.z; v[4 * u + 3] = f.w;
+      } else {
+        const uint2 h = *(const uint2*)(p + k0);
+        v[4 * u] = __uint_as_float(h.x << 16); v[4 * u + 1] = __uint_as_float(h.x & 0xffff0000u);
+        v[4 * u + 2] = __uint_as_float(h.y << 16); v[4 * u + 3] = __uint_as_float(h.y & 0xffff0000u);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < WIDE_E; ++e) {
+      const long k = wide_k<false>(base, tid, e);
+      v[e] = (TAIL && k >= V) ? fill : ld<T>(p + k);
+    }
+  }
+}
+template <typename OT, bool VEC, bool TAIL>
+__device__ __forceinline__ void wide_st(OT* p, long base, long V, int tid, const float (&o)[WIDE_E]) {
+  if constexpr (VEC) {
+#pragma unroll
+    for (int u = 0; u < WIDE_E / 4; ++u) {
+      const long k0 = wide_k<true>(base, tid, 4 * u);
+      if (!TAIL || k0 < V) st4<OT>(p + k0, o[4 * u], o[4 * u + 1], o[4 * u + 2], o[4 * u + 3]);
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < WIDE_E; ++e) {
+      const long k = wide_k<false>(base, tid, e);
+      if (!TAIL || k < V) st<OT>(p + k, o[e]);
+    }
+  }
+}
+// f(base, tail) for every chunk of a row of V: tail is std::true_type for the last chunk when it is partly filled
+template <typename F>
+__device__ __forceinline__ void wide_chunks_up(long V, F&& f) {
+  long base = 0;
+  for (; base + WIDE_C <= V; base += WIDE_C) f(base, std::false_type{});
+  if (base < V) f(base, std::true_type{});
+}
+template <typename F>
+__device__ __forceinline__ void wide_chunks_down(long V, F&& f) {
+  long base = V / WIDE_C * WIDE_C;
+  if (base < V) f(base, std::true_type{});
+  for (base -= WIDE_C; base >= 0; base -= WIDE_C) f(base, std::false_type{});
+}
+
+// block_maxsum in the log2 domain: pairs (m, s) with s = sum of exp2(x - m)
+__device__ __forceinline__ float2 block_maxsum_l2(float m, float s, float* red) {
+  kl_static_for<0, 6>([&](auto sc) {
+    constexpr int S = decltype(sc)::value;
+    const float mo = xpartner<S>(m), so = xpartner<S>(s);
+    const float mn = fmaxf(m, mo);
+    s = (mn == -INFINITY) ? 0.f : s * __builtin_amdgcn_exp2f(m - mn) + so * __builtin_amdgcn_exp2f(mo - mn);
+    m = mn;
+  });
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  __syncthreads();
+  if (lane == 0) { red[2 * w] = m; red[2 * w + 1] = s; }
+  __syncthreads();
+  float M = -INFINITY;
+  for (int i = 0; i < nw; ++i) M = fmaxf(M, red[2 * i]);
+  float S = 0.f;
+  for (int i = 0; i < nw; ++i) S += red[2 * i + 1] * __builtin_amdgcn_exp2f(red[2 * i] - M);
+  return make_float2(M, S);
+}
+
+// (ml, s) of one row: ml = fl(row max * log2 e), s = sum_k exp2(fma(z_k, log2 e, -ml)), exactly the per-element
+// terms the later passes recompute. Online: each thread carries (ml, s) over its elements of every chunk and rescales
+// s by exp2(ml - ml') when a chunk raises ml (a factor of exactly 1 when it does not: the offset stays the rounded
+// product, it is never formed again from the max); block_maxsum_l2 merges the threads' pairs the same way. A thread
+// that has seen padding only keeps ml = -inf, s = 0 (subtracting 0 instead of -inf, as in kl4_fused_kernel).
+template <bool VEC>
+__device__ __forceinline__ float2 wide_maxsum(const float* __restrict__ z, long V, int tid, float* red) {
+  float ml = -INFINITY, s = 0.f;
+  wide_chunks_up(V, [&](long base, auto tail) {
+    float v[WIDE_E];
+    wide_ld<float, VEC, decltype(tail)::value>(z, base, V, tid, v, -INFINITY);
+    float cm = v[0];
+#pragma unroll
+    for (int e = 1; e < WIDE_E; ++e) cm = fmaxf(cm, v[e]);
+    const float mnl = fmaxf(ml, cm * WIDE_L2E);
+    const float off = (mnl == -INFINITY) ? 0.f : mnl;
+    float cs = 0.f;
+#pragma unroll
+    for (int e = 0; e < WIDE_E; ++e) cs += __builtin_amdgcn_exp2f(fmaf(v[e], WIDE_L2E, -off));
+    s = fmaf(s, __builtin_amdgcn_exp2f(ml - off), cs);
+    ml = mnl;
+  });
+  return block_maxsum_l2(ml, s, red);
+}
+
+// BWD = false: fddm_kl_fwd_wide (kl_tok only; mask, dz, B unused). BWD = true: fddm_kl_fused_wide, the three passes
+// of kl4_fused_kernel with the row streamed instead of held: (1) max and sum, (2) the generic log terms and the two
+// gradient sums (the utterance's mask count rides in the same block reduction), (3) the gradient row.
+template <bool VEC, bool BWD, typename OT>
+__global__ void __launch_bounds__(WIDE_NT, KL_WPE) kl_wide_kernel(const float* __restrict__ logits, const long* __restrict__ xt_,
+                                                                  const long* __restrict__ x0_, const long* __restrict__ t_,
+                                                                  const float* __restrict__ betas,
+                                                                  const unsigned char* __restrict__ mask,
+                                                                  float* __restrict__ kl_tok, OT* __restrict__ dz, long L,
+                                                                  long V, long B) {
+  __shared__ float red[2 * (WIDE_NT / 64) + 4 * (WIDE_NT / 64)];
+  const long row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const float* z = logits + row * V;
+  const long xt = xt_[row], x0 = x0_[row], b = row / L, tv = t_[b];
+  const float eps = 1e-8f;
+  const KlRow c = kl_consts(betas, tv, xt, x0, (float)V);
+  const float zxt = z[xt], zx0 = z[x0];
+
+  const float2 ms = wide_maxsum<VEC>(z, V, tid, red);
+  const float mxl = ms.x, inv_s = 1.f / ms.y;
+  // the special indices' probabilities exactly as passes 2 and 3 form them for every element
+  const float xhat_xt = __builtin_amdgcn_exp2f(fmaf(zxt, WIDE_L2E, -mxl)) * inv_s;
+  const float xhat_x0 = __builtin_amdgcn_exp2f(fmaf(zx0, WIDE_L2E, -mxl)) * inv_s;
+  const float dp = c.b_t + c.a_t * xhat_xt;
+  const float inv_dp = 1.f / (dp + eps);
+  const float Qg = c.b_t * c.b_p * c.inv_dq;
+  const float LQg = __logf(Qg + eps);
+  auto special = [&](long k, float xh, float& P, float& Q, float& M) {
+    M = c.b_t + (k == xt ? c.a_t : 0.f);
+    Q = M * ((k == x0 ? c.a_p : 0.f) + c.b_p) * c.inv_dq;
+    P = M * (c.a_p * xh + c.b_p) * inv_dp;
+  };
+  const float pa = c.b_t * c.a_p * inv_dp, pb = c.b_t * c.b_p * inv_dp, pbe = pb + eps;
+  const long ks[2] = {xt, x0};
+  const float xs[2] = {xhat_xt, xhat_x0};
+  const int nsp = (xt == x0) ? 1 : 2;
+
+  // pass 2, last chunk first. sum_k log(P_k + eps) as the log of each group of four factors (each >= eps = 1e-8: the
+  // product stays a normal f32, so the raw log2 instruction serves); sum_k P_k / (P_k + eps) = V - eps sum_k 1 / (P_k +
+  // eps). Padding lanes of the last chunk contribute a factor 1 and no count.
+  float acc = 0.f, sr = 0.f, a2 = 0.f, cnt = 0.f;
+  wide_chunks_down(V, [&](long base, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    float v[WIDE_E];
+    wide_ld<float, VEC, TAIL>(z, base, V, tid, v, -INFINITY);
+#pragma unroll
+    for (int u = 0; u < WIDE_E / 4; ++u) {
+      float prod = 1.f, n = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = 4 * u + j;
+        const bool ok = !TAIL || wide_k<VEC>(base, tid, e) < V;
+        const float xh = __builtin_amdgcn_exp2f(fmaf(v[e], WIDE_L2E, -mxl)) * inv_s;
+        const float Pe = fmaf(pa, xh, pbe);
+        prod *= ok ? Pe : 1.f;
+        n += ok ? 1.f : 0.f;
+        if constexpr (BWD) {
+          const float r = ok ? __builtin_amdgcn_rcpf(Pe) : 0.f;
+          sr += r;
+          a2 = fmaf(xh, r, a2);
+        }
+      }
+      acc += fmaf(-0.6931471805599453f, __builtin_amdgcn_logf(prod), n * LQg);
+    }
+  });
+  float4 sums;
+  if constexpr (BWD) {
+    if (mask)
+      for (long l = tid; l < L; l += WIDE_NT) cnt += mask[b * L + l] ? 1.f : 0.f;
+    sums = block_sum4(acc, sr, a2, cnt, red + 2 * (WIDE_NT / 64));
+    sums.y = (float)V - eps * sums.y;
+  } else {
+    sums = make_float4(block_sum(acc, red + 2 * (WIDE_NT / 64)), 0.f, 0.f, 0.f);
+  }
+  if (tid == 0) {
+    float kl = Qg * sums.x;
+    for (int j = 0; j < nsp; ++j) {
+      float P, Q, M;
+      special(ks[j], xs[j], P, Q, M);
+      kl += Q * (__logf(Q + eps) - __logf(P + eps)) - Qg * (LQg - __logf(fmaf(pa, xs[j], pb) + eps));
+    }
+    kl_tok[row] = kl;
+  }
+  if constexpr (BWD) {
+    const float gc = -Qg * c.b_t * c.a_p * inv_dp;
+    float s1 = Qg * sums.y, g0s = gc * sums.z;
+    for (int j = 0; j < nsp; ++j) {
+      float P, Q, M;
+      special(ks[j], xs[j], P, Q, M);
+      const float Pg = fmaf(pa, xs[j], pb);
+      s1 += Q * P / (P + eps) - Qg * Pg / (Pg + eps);
+      g0s += -Q * M * c.a_p / (P + eps) * inv_dp * xs[j] - gc * xs[j] / (Pg + eps);
+    }
+    const float gxt = c.a_t * s1 * inv_dp;
+    const float G = g0s + xhat_xt * gxt;
+    const float wr = mask ? ((mask[row] ? 1.f : 0.f) / (sums.w + eps) / (float)B) : 1.f / ((float)L * (float)B);
+    const float wgc = wr * gc, wG = wr * G;
+    OT* out = dz + row * V;
+    // pass 3, first chunk first (pass 2 ended there)
+    wide_chunks_up(V, [&](long base, auto tail) {
+      constexpr bool TAIL = decltype(tail)::value;
+      float v[WIDE_E], o[WIDE_E];
+      wide_ld<float, VEC, TAIL>(z, base, V, tid, v, -INFINITY);
+#pragma unroll
+      for (int e = 0; e < WIDE_E; ++e) {
+        v[e] = __builtin_amdgcn_exp2f(fmaf(v[e], WIDE_L2E, -mxl)) * inv_s;
+        o[e] = v[e] * fmaf(wgc, __builtin_amdgcn_rcpf(fmaf(pa, v[e], pbe)), -wG);
+      }
+      // the chunk that holds x_t and / or x0 (uniform test): exact per-index terms for those elements
+      if ((xt >= base && xt < base + WIDE_C) || (x0 >= base && x0 < base + WIDE_C)) {
+#pragma unroll
+        for (int e = 0; e < WIDE_E; ++e) {
+          const long k = wide_k<VEC>(base, tid, e);
+          if (k == xt || k == x0) {
+            float P, Q, M;
+            special(k, v[e], P, Q, M);
+            const float g = -Q * M * c.a_p / (P + eps) * inv_dp + (k == xt ? gxt : 0.f);
+            o[e] = wr * v[e] * (g - G);
+          }
+        }
+      }
+      wide_st<OT, VEC, TAIL>(out, base, V, tid, o);
+    });
+  }
+}
+
+// softmax of one streamed row: f32 in, f32 or bf16 out
+template <bool VEC, typename OT>
+__global__ void __launch_bounds__(WIDE_NT) softmax_wide_kernel(const float* __restrict__ x, OT* __restrict__ y, long V) {
+  __shared__ float red[2 * (WIDE_NT / 64)];
+  const long row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const float* z = x + row * V;
+  const float2 ms = wide_maxsum<VEC>(z, V, tid, red);
+  const float mxl = ms.x, inv_s = 1.f / ms.y;
+  wide_chunks_down(V, [&](long base, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    float v[WIDE_E];
+    wide_ld<float, VEC, TAIL>(z, base, V, tid, v, -INFINITY);
+#pragma unroll
+    for (int e = 0; e < WIDE_E; ++e) v[e] = __builtin_amdgcn_exp2f(fmaf(v[e], WIDE_L2E, -mxl)) * inv_s;
+    wide_st<OT, VEC, TAIL>(y + row * V, base, V, tid, v);
+  });
+}
+
+// dz (f32) = y (dy - sum(y dy)) [+ dz] over one streamed row; y, dy f32 or bf16
+template <bool VEC, typename T>
+__global__ void __launch_bounds__(WIDE_NT) softmax_bwd_wide_kernel(const T* __restrict__ y, const T* __restrict__ dy,
+                                                                   float* __restrict__ dz, long V, int accumulate) {
+  __shared__ float red[WIDE_NT / 64];
+  const long row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const T* yr = y + row * V;
+  const T* dr = dy + row * V;
+  float* o = dz + row * V;
+  float s = 0.f;
+  wide_chunks_up(V, [&](long base, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    float a[WIDE_E], d[WIDE_E];
+    wide_ld<T, VEC, TAIL>(yr, base, V, tid, a, 0.f);
+    wide_ld<T, VEC, TAIL>(dr, base, V, tid, d, 0.f);
+#pragma unroll
+    for (int e = 0; e < WIDE_E; ++e) s = fmaf(a[e], d[e], s);
+  });
+  s = block_sum(s, red);
+  wide_chunks_down(V, [&](long base, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    float a[WIDE_E], d[WIDE_E];
+    wide_ld<T, VEC, TAIL>(yr, base, V, tid, a, 0.f);
+    wide_ld<T, VEC, TAIL>(dr, base, V, tid, d, 0.f);
+#pragma unroll
+    for (int e = 0; e < WIDE_E; ++e) a[e] *= d[e] - s;
+    if (accumulate) {
+      wide_ld<float, VEC, TAIL>(o, base, V, tid, d, 0.f);
+#pragma unroll
+      for (int e = 0; e < WIDE_E; ++e) a[e] += d[e];
+    }
+    wide_st<float, VEC, TAIL>(o, base, V, tid, a);
+  });
+}
+
+// out = bf16(y (dy - sum(y dy)) + add) over one streamed row, all bf16 (V % 8 == 0). out may be add: a thread reads
+// its elements of add before it writes them, so neither carries __restrict__.
+__global__ void __launch_bounds__(WIDE_NT) softmax_bwd_add_wide_kernel(const bf16_t* __restrict__ y,
+                                                                       const bf16_t* __restrict__ dy, const bf16_t* add,
+                                                                       bf16_t* out, long V) {
+  __shared__ float red[WIDE_NT / 64];
+  const long row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const bf16_t* yr = y + row * V;
+  const bf16_t* dr = dy + row * V;
+  float s = 0.f;
+  wide_chunks_up(V, [&](long base, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    float a[WIDE_E], d[WIDE_E];
+    wide_ld<bf16_t, true, TAIL>(yr, base, V, tid, a, 0.f);
+    wide_ld<bf16_t, true, TAIL>(dr, base, V, tid, d, 0.f);
+#pragma unroll
+    for (int e = 0; e < WIDE_E; ++e) s = fmaf(a[e], d[e], s);
+  });
+  s = block_sum(s, red);
+  wide_chunks_down(V, [&](long base, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    float a[WIDE_E], d[WIDE_E], c[WIDE_E];
+    wide_ld<bf16_t, true, TAIL>(yr, base, V, tid, a, 0.f);
+    wide_ld<bf16_t, true, TAIL>(dr, base, V, tid, d, 0.f);
+    wide_ld<bf16_t, true, TAIL>(add + row * V, base, V, tid, c, 0.f);
+#pragma unroll
+    for (int e = 0; e < WIDE_E; ++e) a[e] = a[e] * (d[e] - s) + c[e];
+    wide_st<bf16_t, true, TAIL>(out + row * V, base, V, tid, a);
+  });
+}
+
 }  // namespace fddm
 
 using namespace fddm;
@@ -898,5 +1237,94 @@ FDDM_API int fddm_axpy_if_bf16(void* x, const void* y, const float* g, long n, v
   const long want = (n / 8 + 255) / 256;
   const unsigned grid = (unsigned)(want < 4096 ? want : 4096);
   hipLaunchKernelGGL(axpy_if_kernel, dim3(grid), dim3(256), 0, (hipStream_t)hs, (bf16_t*)x, (const bf16_t*)y, g, n / 8);
+  return (int)hipGetLastError();
+}
+
+// ---- streamed forms of the row kernels above for 2 <= V <= 2^24 (fddm_hip.h, KL section): any V and alignment; the
+// vector instantiation serves V % 4 == 0 with 16-byte-aligned operands, the scalar one everything else
+static inline bool wide_v_ok(long V) { return V >= 2 && V <= WIDE_MAX_V; }
+static inline bool wide_n_ok(long N) { return N >= 0 && N <= 0x7fffffffL; }  // one workgroup per row: gridDim.x
+
+// elements per workgroup iteration of the streamed kernels (tests place their cases on its multiples)
+FDDM_API long fddm_wide_chunk(void) { return WIDE_C; }
+static inline bool wide_al16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return !((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15);
+}
+
+FDDM_API int fddm_kl_fwd_wide(const float* logits, const long* xt, const long* x0, const long* t, const float* betas,
+                              float* kl_tok, long N, long L, long V, void* hs) {
+  if (!wide_v_ok(V) || L <= 0 || !wide_n_ok(N) || N % L) return (int)hipErrorInvalidValue;
+  if (N == 0) return 0;
+  hipStream_t s = (hipStream_t)hs;
+  if (V % 4 == 0 && wide_al16(logits))
+    hipLaunchKernelGGL((kl_wide_kernel<true, false, float>), dim3((unsigned)N), dim3(WIDE_NT), 0, s, logits, xt, x0, t,
+                       betas, (const unsigned char*)nullptr, kl_tok, (float*)nullptr, L, V, N / L);
+  else
+    hipLaunchKernelGGL((kl_wide_kernel<false, false, float>), dim3((unsigned)N), dim3(WIDE_NT), 0, s, logits, xt, x0, t,
+                       betas, (const unsigned char*)nullptr, kl_tok, (float*)nullptr, L, V, N / L);
+  return (int)hipGetLastError();
+}
+
+#define KLW_LAUNCH(VEC)                                                                                              \
+  do {                                                                                                               \
+    if (dz_dtype == FDDM_BF16)                                                                                       \
+      hipLaunchKernelGGL((kl_wide_kernel<VEC, true, bf16_t>), dim3((unsigned)N), dim3(WIDE_NT), 0, s, logits, xt, x0, \
+                         t, betas, mask, kl_tok, (bf16_t*)dz, L, V, N / L);                                          \
+    else                                                                                                             \
+      hipLaunchKernelGGL((kl_wide_kernel<VEC, true, float>), dim3((unsigned)N), dim3(WIDE_NT), 0, s, logits, xt, x0,  \
+                         t, betas, mask, kl_tok, (float*)dz, L, V, N / L);                                           \
+  } while (0)
+
+FDDM_API int fddm_kl_fused_wide(const float* logits, const long* xt, const long* x0, const long* t, const float* betas,
+                                const unsigned char* mask, float* kl_tok, void* dz, int dz_dtype, long N, long L,
+                                long V, void* hs) {
+  if (!wide_v_ok(V) || L <= 0 || !wide_n_ok(N) || N % L || (dz_dtype != FDDM_BF16 && dz_dtype != FDDM_F32))
+    return (int)hipErrorInvalidValue;
+  if (N == 0) return 0;
+  hipStream_t s = (hipStream_t)hs;
+  if (V % 4 == 0 && wide_al16(logits, dz)) KLW_LAUNCH(true);
+  else KLW_LAUNCH(false);
+  return (int)hipGetLastError();
+}
+
+FDDM_API int fddm_softmax_rows_wide(const float* x, void* y, int out_dtype, long N, long V, void* hs) {
+  if (!wide_v_ok(V) || !wide_n_ok(N) || (out_dtype != FDDM_BF16 && out_dtype != FDDM_F32)) return (int)hipErrorInvalidValue;
+  if (N == 0) return 0;
+  hipStream_t s = (hipStream_t)hs;
+  const bool vec = V % 4 == 0 && wide_al16(x, y);
+  const dim3 g((unsigned)N), b(WIDE_NT);
+  if (out_dtype == FDDM_BF16) {
+    if (vec) hipLaunchKernelGGL((softmax_wide_kernel<true, bf16_t>), g, b, 0, s, x, (bf16_t*)y, V);
+    else hipLaunchKernelGGL((softmax_wide_kernel<false, bf16_t>), g, b, 0, s, x, (bf16_t*)y, V);
+  } else {
+    if (vec) hipLaunchKernelGGL((softmax_wide_kernel<true, float>), g, b, 0, s, x, (float*)y, V);
+    else hipLaunchKernelGGL((softmax_wide_kernel<false, float>), g, b, 0, s, x, (float*)y, V);
+  }
+  return (int)hipGetLastError();
+}
+
+FDDM_API int fddm_softmax_bwd_rows_wide(const void* y, const void* dy, float* dz, int dtype, long N, long V,
+                                        int accumulate, void* hs) {
+  if (!wide_v_ok(V) || !wide_n_ok(N) || (dtype != FDDM_BF16 && dtype != FDDM_F32)) return (int)hipErrorInvalidValue;
+  if (N == 0) return 0;
+  hipStream_t s = (hipStream_t)hs;
+  const bool vec = V % 4 == 0 && wide_al16(y, dy, dz);
+  const dim3 g((unsigned)N), b(WIDE_NT);
+  if (dtype == FDDM_BF16) {
+    if (vec) hipLaunchKernelGGL((softmax_bwd_wide_kernel<true, bf16_t>), g, b, 0, s, (const bf16_t*)y, (const bf16_t*)dy, dz, V, accumulate);
+    else hipLaunchKernelGGL((softmax_bwd_wide_kernel<false, bf16_t>), g, b, 0, s, (const bf16_t*)y, (const bf16_t*)dy, dz, V, accumulate);
+  } else {
+    if (vec) hipLaunchKernelGGL((softmax_bwd_wide_kernel<true, float>), g, b, 0, s, (const float*)y, (const float*)dy, dz, V, accumulate);
+    else hipLaunchKernelGGL((softmax_bwd_wide_kernel<false, float>), g, b, 0, s, (const float*)y, (const float*)dy, dz, V, accumulate);
+  }
+  return (int)hipGetLastError();
+}
+
+FDDM_API int fddm_softmax_bwd_add_bf16_wide(const void* y, const void* dy, const void* add, void* out, long N, long V,
+                                            void* hs) {
+  if (!wide_v_ok(V) || !wide_n_ok(N) || V % 8 || !wide_al16(y, dy, add) || !wide_al16(out)) return (int)hipErrorInvalidValue;
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(softmax_bwd_add_wide_kernel, dim3((unsigned)N), dim3(WIDE_NT), 0, (hipStream_t)hs,
+                     (const bf16_t*)y, (const bf16_t*)dy, (const bf16_t*)add, (bf16_t*)out, V);
   return (int)hipGetLastError();
 }

@@ -461,6 +461,13 @@ class HeadFn(torch.autograd.Function):
 
 
 # -------------------------------------------------------------------------------------- KL term
+def _kl_resident(V, l2):
+    """Whether fddm_kl_fwd / fddm_kl_bwd (a row held in registers) serve rows of V at this address (ops._chk_kl_vocab);
+    past that the streamed *_wide kernels take the row."""
+    vec = V % 4 == 0 and l2.data_ptr() % 16 == 0
+    return V <= (ops.KL_VEC_MAX_V if vec else ops.KL_SCALAR_MAX_V)
+
+
 class KLFn(torch.autograd.Function):
     """SchedulerAdapter.kl_term (train.py:190-255): fused closed-form KL. With a gradient wanted, ONE pass over the
     logits produces the per-token KL and its logits gradient (times the masked-mean weights); backward only applies
@@ -476,7 +483,10 @@ class KLFn(torch.autograd.Function):
         ctx.shape = (B, L, V)
         ctx.handover = None
         if not ctx.needs_input_grad[0]:
-            kl_tok = ops.kl_fwd(l2, xf, x0f, tc, betas, L)
+            if _kl_resident(V, l2):
+                kl_tok = ops.kl_fwd(l2, xf, x0f, tc, betas, L)
+            else:
+                kl_tok = ops.kl_fwd_wide(l2.contiguous(), xf, x0f, tc, betas, L)
             loss, _ = ops.kl_reduce(kl_tok, mask_u8, B, L, want_w=False)
             return loss
         ptr = l2.data_ptr()
@@ -491,14 +501,18 @@ class KLFn(torch.autograd.Function):
         if V % 4 == 0 and V <= ops.KL_FUSED_MAX_V and l2.data_ptr() % 16 == 0:
             kl_tok, dz = ops.kl_fused(l2, xf, x0f, tc, betas, mask_u8, L, out_dtype=odt)
             loss, _ = ops.kl_reduce(kl_tok, mask_u8, B, L, want_w=False)
-        else:
+        elif _kl_resident(V, l2):
             # rows the one-pass kernel is not built for (V % 4 != 0 or unaligned rows, up to V = 16384): the two-pass
-            # form — per-token KL, the masked-mean weights, then the weighted gradient. No kernel serves V > 32768
-            # (or V > 16384 on this path): ops.kl_fwd raises a ValueError there
+            # form — per-token KL, the masked-mean weights, then the weighted gradient
             kl_tok = ops.kl_fwd(l2, xf, x0f, tc, betas, L)
             loss, w = ops.kl_reduce(kl_tok, mask_u8, B, L, want_w=True)
             one = torch.ones(1, device=l2.device, dtype=F32)
             dz = ops.kl_bwd(l2, xf, x0f, tc, betas, w, one, L, out_dtype=odt)
+        else:
+            # beyond the resident kernels (V > 32768, or V > 16384 with V % 4 != 0 or unaligned rows): the streamed
+            # one-pass-equivalent kernel, any V up to ops.WIDE_MAX_V (a ValueError beyond) and any alignment
+            kl_tok, dz = ops.kl_fused_wide(l2, xf, x0f, tc, betas, mask_u8, L, out_dtype=odt)
+            loss, _ = ops.kl_reduce(kl_tok, mask_u8, B, L, want_w=False)
         ctx.dz = dz
         if bf:
             ctx.handover = ptr
@@ -533,7 +547,8 @@ class TextEmbedFn(torch.autograd.Function):
         V = shp[-1]
         l2 = logits.reshape(-1, V).contiguous()
         cd = rt.compute_dtype()
-        xhat = ops.softmax_rows(l2, cd)
+        # past the resident kernel's row (V > 16384) the streamed form; ops raises beyond ops.WIDE_MAX_V
+        xhat = ops.softmax_rows(l2, cd) if V <= ops.SOFTMAX_MAX_V else ops.softmax_rows_wide(l2, cd)
         z = ops.linear(xhat, rt.wt(weight), None, out_dtype=F32)
         ctx.save_for_backward(xhat, weight)
         ctx.shp = shp
@@ -555,10 +570,12 @@ class TextEmbedFn(torch.autograd.Function):
         if (kl is not None and cd == torch.bfloat16 and ptr in _head_outputs and ptr not in _dlogits_bf16
                 and ptr not in _combined and xhat.shape[-1] % 8 == 0):     # fddm_softmax_bwd_add_bf16: V % 8 == 0
             # bf16 hand-over: softmax backward + the KL's (unscaled) share in one bf16 buffer for HeadFn
-            _dlogits_bf16[ptr] = ops.softmax_bwd_add_bf16(xhat, dxhat, kl)
+            add = ops.softmax_bwd_add_bf16 if xhat.shape[-1] <= ops.SOFTMAX_ADD_MAX_V else ops.softmax_bwd_add_bf16_wide
+            _dlogits_bf16[ptr] = add(xhat, dxhat, kl)
             _combined.add(ptr)
             return None, dW
-        dlogits = ops.softmax_bwd_rows(xhat, dxhat)
+        bwd = ops.softmax_bwd_rows if xhat.shape[-1] <= ops.SOFTMAX_MAX_V else ops.softmax_bwd_rows_wide
+        dlogits = bwd(xhat, dxhat)
         return dlogits.view(ctx.shp), dW
 
 

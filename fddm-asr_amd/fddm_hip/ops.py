@@ -839,6 +839,8 @@ KL_VEC_MAX_V = 32768        # fddm_kl_fwd/_bwd float4 kernels: V % 4 == 0 and 16
 KL_SCALAR_MAX_V = 16384     # fddm_kl_fwd/_bwd scalar kernel (any V, any alignment): 256 threads x 64 elements
 KL_FUSED_MAX_V = 32768      # fddm_kl_fused (V % 4 == 0, aligned rows only): 512 threads x 16 float4 per row
 SOFTMAX_MAX_V = 16384       # fddm_softmax_rows/_bwd_rows: 256 threads x 64 elements
+SOFTMAX_ADD_MAX_V = 32768   # fddm_softmax_bwd_add_bf16 (V % 8 == 0): 256 threads x 16 loads of 8 bf16
+WIDE_MAX_V = 1 << 24        # the streamed *_wide forms: 2 <= V <= 2^24 ((float)V exact), any V % 4, any alignment
 
 
 def _chk_kl_vocab(name, V, *bufs):
@@ -924,6 +926,104 @@ def softmax_bwd_rows(y, dy, dz=None, accumulate=False):
         dz = torch.empty(N, V, device=y.device, dtype=torch.float32)
     call("fddm_softmax_bwd_rows", ptr(y), ptr(dy), ptr(dz), code(y), N, V, int(accumulate), stream())
     return dz
+
+
+# ---- the streamed forms (csrc/kl.hip, "wide" kernels): any 2 <= V <= WIDE_MAX_V, any alignment. The kernels index
+# every operand as contiguous [N, V] rows from a raw pointer, so each wrapper checks shape, dtype, layout and device.
+def _chk_wide_vocab(name, V):
+    if not 2 <= V <= WIDE_MAX_V:
+        raise ValueError(f"{name}: V = {V} is outside the supported range 2 <= V <= {WIDE_MAX_V}")
+
+
+def _chk_wide_rows(name, what, t, N, V, dtypes, dev):
+    _chk(t.dim() == 2 and tuple(t.shape) == (N, V) and t.is_contiguous() and t.dtype in dtypes and t.device == dev,
+         f"{name}: {what} is contiguous [N, V], " + " or ".join(str(x)[6:] for x in dtypes) + ", on the input's GPU")
+
+
+def _chk_wide_kl(name, logits2d, xt, x0, t, betas, L):
+    _chk(logits2d.dim() == 2, f"{name}: logits are [B*L, V]")
+    N, V = logits2d.shape
+    _chk_wide_vocab(name, V)
+    dev = logits2d.device
+    _chk(logits2d.is_cuda, f"{name}: logits are on a GPU")
+    _chk_wide_rows(name, "logits", logits2d, N, V, (_F32,), dev)
+    _chk(L > 0 and N % L == 0, f"{name}: N is a multiple of L > 0")
+    for what, i, n in (("xt", xt, N), ("x0", x0, N), ("t", t, N // L)):
+        _chk(i.dtype == torch.long and i.numel() == n and i.is_contiguous() and i.device == dev,
+             f"{name}: {what} holds {n} contiguous int64 on the logits' GPU")
+    _chk(betas.dtype == _F32 and betas.is_contiguous() and betas.device == dev, f"{name}: betas are contiguous f32")
+    return N, V
+
+
+def kl_fwd_wide(logits2d, xt, x0, t, betas, L, kl_tok=None):
+    """kl_tok [N] f32 as kl_fwd, the row streamed (any V up to WIDE_MAX_V, any alignment)."""
+    N, V = _chk_wide_kl("kl_fwd_wide", logits2d, xt, x0, t, betas, L)
+    if kl_tok is None:
+        kl_tok = torch.empty(N, device=logits2d.device, dtype=_F32)
+    _chk(kl_tok.dtype == _F32 and kl_tok.numel() == N and kl_tok.is_contiguous() and kl_tok.device == logits2d.device,
+         "kl_fwd_wide: kl_tok is contiguous f32 [N]")
+    call("fddm_kl_fwd_wide", ptr(logits2d), ptr(xt), ptr(x0), ptr(t), ptr(betas), ptr(kl_tok), N, L, V, stream())
+    return kl_tok
+
+
+def kl_fused_wide(logits2d, xt, x0, t, betas, mask_u8, L, out_dtype=torch.float32, kl_tok=None, dz=None):
+    """(kl_tok [N] f32, dz [N, V]) as kl_fused, the row streamed: also V % 4 != 0 and rows that are not 16-byte
+    aligned. kl_tok / dz: optional destinations (dz decides the output dtype)."""
+    N, V = _chk_wide_kl("kl_fused_wide", logits2d, xt, x0, t, betas, L)
+    dev = logits2d.device
+    _chk(mask_u8 is None or (mask_u8.numel() == N and mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+                             and mask_u8.device == dev), "kl_fused_wide: mask is contiguous uint8 [N]")
+    if kl_tok is None:
+        kl_tok = torch.empty(N, device=dev, dtype=_F32)
+    if dz is None:
+        dz = torch.empty(N, V, device=dev, dtype=out_dtype)
+    _chk(kl_tok.dtype == _F32 and kl_tok.numel() == N and kl_tok.is_contiguous() and kl_tok.device == dev,
+         "kl_fused_wide: kl_tok is contiguous f32 [N]")
+    _chk_wide_rows("kl_fused_wide", "dz", dz, N, V, _FLOATS, dev)
+    call("fddm_kl_fused_wide", ptr(logits2d), ptr(xt), ptr(x0), ptr(t), ptr(betas), ptr(mask_u8), ptr(kl_tok),
+         ptr(dz), code(dz), N, L, V, stream())
+    return kl_tok, dz
+
+
+def softmax_rows_wide(x2d, out_dtype, out=None):
+    _chk(x2d.dim() == 2 and x2d.is_cuda, "softmax_rows_wide: the input is [N, V] on a GPU")
+    N, V = x2d.shape
+    _chk_wide_vocab("softmax_rows_wide", V)
+    _chk_wide_rows("softmax_rows_wide", "x", x2d, N, V, (_F32,), x2d.device)
+    if out is None:
+        out = torch.empty(N, V, device=x2d.device, dtype=out_dtype)
+    _chk_wide_rows("softmax_rows_wide", "out", out, N, V, _FLOATS, x2d.device)
+    call("fddm_softmax_rows_wide", ptr(x2d), ptr(out), code(out), N, V, stream())
+    return out
+
+
+def softmax_bwd_rows_wide(y, dy, dz=None, accumulate=False):
+    _chk(y.dim() == 2 and y.is_cuda, "softmax_bwd_rows_wide: y is [N, V] on a GPU")
+    N, V = y.shape
+    _chk_wide_vocab("softmax_bwd_rows_wide", V)
+    _chk_wide_rows("softmax_bwd_rows_wide", "y", y, N, V, _FLOATS, y.device)
+    _chk_wide_rows("softmax_bwd_rows_wide", "dy", dy, N, V, (y.dtype,), y.device)
+    _chk(dz is not None or not accumulate, "softmax_bwd_rows_wide: accumulate needs dz")
+    if dz is None:
+        dz = torch.empty(N, V, device=y.device, dtype=_F32)
+    _chk_wide_rows("softmax_bwd_rows_wide", "dz", dz, N, V, (_F32,), y.device)
+    call("fddm_softmax_bwd_rows_wide", ptr(y), ptr(dy), ptr(dz), code(y), N, V, int(accumulate), stream())
+    return dz
+
+
+def softmax_bwd_add_bf16_wide(y, dy, add, out=None):
+    """out = bf16(y * (dy - rowsum(y*dy)) + add), all bf16 [N, V], V % 8 == 0 (out may be `add`), the row streamed."""
+    _chk(y.dim() == 2 and y.is_cuda, "softmax_bwd_add_bf16_wide: y is [N, V] on a GPU")
+    N, V = y.shape
+    _chk_wide_vocab("softmax_bwd_add_bf16_wide", V)
+    _chk(V % 8 == 0, "softmax_bwd_add_bf16_wide: V % 8 == 0")
+    if out is None:
+        out = torch.empty_like(y)
+    for what, t in (("y", y), ("dy", dy), ("add", add), ("out", out)):
+        _chk_wide_rows("softmax_bwd_add_bf16_wide", what, t, N, V, (torch.bfloat16,), y.device)
+        _chk(t.data_ptr() % 16 == 0, f"softmax_bwd_add_bf16_wide: {what} is 16-byte aligned")
+    call("fddm_softmax_bwd_add_bf16_wide", ptr(y), ptr(dy), ptr(add), ptr(out), N, V, stream())
+    return out
 
 
 def _chk_lfd(name, z, zt=None, vecs=()):

@@ -245,11 +245,15 @@ int fddm_transpose_bf16_mt(const long* table, long ntensors, long nblocks, void*
 
 /* ---- discrete diffusion: q_sample draw (train.py:180-188; diffusion_scheduler.py:31-50) and the
  *      categorical KL + exact gradient (train.py:190-255). thr: [T] uint32 keep thresholds.
- *      Vocabulary limits (one workgroup holds a row in registers; beyond them the call returns
- *      hipErrorInvalidValue without a launch, and fddm_hip/ops.py raises a ValueError first):
+ *      Vocabulary limits. The resident kernels hold a row in the registers of one workgroup; beyond their limits
+ *      the call returns hipErrorInvalidValue without a launch, and fddm_hip/ops.py raises a ValueError first:
  *        fddm_kl_fwd / fddm_kl_bwd: V <= 32768 when V % 4 == 0 and logits and dz are 16-byte aligned, else V <= 16384;
  *        fddm_kl_fused: V <= 32768, V % 4 == 0 and aligned rows only;
- *        fddm_softmax_rows / fddm_softmax_bwd_rows: V <= 16384; fddm_softmax_bwd_add_bf16: V <= 32768, V % 8 == 0. */
+ *        fddm_softmax_rows / fddm_softmax_bwd_rows: V <= 16384; fddm_softmax_bwd_add_bf16: V <= 32768, V % 8 == 0.
+ *      The *_wide forms stream the row in chunks of 8192 elements instead (one more read of the row per pass) and
+ *      serve 2 <= V <= 2^24 (where (float)V is exact), any V and any row alignment (a scalar-access instantiation
+ *      takes V % 4 != 0 and operands that are not 16-byte aligned); outside that range they return
+ *      hipErrorInvalidValue without a launch. fddm_hip/functions.py takes them only where no resident kernel serves. */
 int fddm_sample_q(const long* x0, const long* t, const unsigned* thr, long* xt, long B, long L, long K,
                   unsigned long long seed, unsigned long long stream, void* hip_stream);
 int fddm_kl_fwd(const float* logits, const long* xt, const long* x0, const long* t, const float* betas, float* kl_tok,
@@ -274,6 +278,22 @@ int fddm_axpy_if_bf16(void* x, const void* y, const float* g, long n, void* hip_
 int fddm_softmax_rows(const float* x, void* y, int out_dtype, long N, long V, void* hip_stream);
 int fddm_softmax_bwd_rows(const void* y, const void* dy, float* dz, int dtype, long N, long V, int accumulate,
                           void* hip_stream);
+
+/* ---- streamed forms for 2 <= V <= 2^24 (limits: the KL section above). Arguments and results as fddm_kl_fwd,
+ *      fddm_kl_fused (also V % 4 != 0 and unaligned rows: it replaces fddm_kl_fwd + fddm_kl_reduce + fddm_kl_bwd at
+ *      wide V), fddm_softmax_rows, fddm_softmax_bwd_rows and fddm_softmax_bwd_add_bf16 (V % 8 == 0, 16-byte-aligned
+ *      operands, out may alias add). */
+long fddm_wide_chunk(void); /* elements per workgroup iteration (8192); N <= 2^31 - 1 rows per call */
+int fddm_kl_fwd_wide(const float* logits, const long* xt, const long* x0, const long* t, const float* betas,
+                     float* kl_tok, long N, long L, long V, void* hip_stream);
+int fddm_kl_fused_wide(const float* logits, const long* xt, const long* x0, const long* t, const float* betas,
+                       const unsigned char* mask, float* kl_tok, void* dz, int dz_dtype, long N, long L, long V,
+                       void* hip_stream);
+int fddm_softmax_rows_wide(const float* x, void* y, int out_dtype, long N, long V, void* hip_stream);
+int fddm_softmax_bwd_rows_wide(const void* y, const void* dy, float* dz, int dtype, long N, long V, int accumulate,
+                               void* hip_stream);
+int fddm_softmax_bwd_add_bf16_wide(const void* y, const void* dy, const void* add, void* out, long N, long V,
+                                   void* hip_stream);
 
 /* ---- L_fd (losses/fddm_losses.py:18-58): batch-dim standardisation and the Barlow-Twins loss */
 int fddm_lfd_std_fwd(int out_dtype, const float* z, void* zt, float* inv_std, long B, long C, float eps,
