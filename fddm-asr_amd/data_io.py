@@ -8,6 +8,10 @@ constructor, filtering, audio/token padding and item layout, built on what this 
   and librosa's channel mean for multi-channel files, so those clips load bit-identically. A clip at another rate
   is resampled with a polyphase filter (scipy.signal.resample_poly): librosa's default soxr_hq resampler is not
   in the image, so that case is close to, not identical with, the reference (never produced by its preprocessor).
+* Inference audio. `read_wav` is that container parser with the channels kept apart; `load_batch` turns files of any
+  rate and 1 - 8 channels into a padded 16 kHz batch on the GPU: the channel mean and torchaudio's sinc resampler (what
+  the reference's inference.py:53-61 applies) run in `fddm_wav_resample` (csrc/audio.hip), one launch per source rate.
+  `load_wav_16k` keeps its scipy resampler: the training path never meets another rate.
 * Text. `tokenizer.encode(item["normalized_sentence"])` with the SentencePiece model at `tokenizer_vocab_path`.
   When the binary `.model` is absent (the reference ships only `spm_zhTW_A.vocab` + `vocab.json`),
   `load_tokenizer` rebuilds the BPE model from the `.vocab` (piece, score) table — the reference trains it as
@@ -31,9 +35,9 @@ TARGET_SR = 16000
 _WAVE_PCM, _WAVE_FLOAT, _WAVE_EXT = 1, 3, 0xFFFE
 
 
-def load_wav_16k(path: str, target_sr: int = TARGET_SR) -> np.ndarray:
-    """float32 mono samples of a RIFF/WAVE file at `target_sr` (librosa.load(path, sr=target_sr) for the
-    reference's preprocessed clips; see the module docstring)."""
+def read_wav(path: str):
+    """(float32 samples [n, nch], sample rate) of a RIFF/WAVE file: the container parser and the integer scaling of
+    `load_wav_16k` (PCM 8/16/24/32-bit, IEEE float 32/64, WAVE_FORMAT_EXTENSIBLE), channels kept apart."""
     with open(path, "rb") as f:
         blob = f.read()
     if len(blob) < 12 or blob[:4] != b"RIFF" or blob[8:12] != b"WAVE":
@@ -73,6 +77,14 @@ def load_wav_16k(path: str, target_sr: int = TARGET_SR) -> np.ndarray:
         x = raw.copy().view("<f4" if width == 4 else "<f8")[..., 0].astype(np.float32)
     else:
         raise ValueError(f"{path}: WAVE format tag {tag:#x} is not supported")
+    return x, sr
+
+
+def load_wav_16k(path: str, target_sr: int = TARGET_SR) -> np.ndarray:
+    """float32 mono samples of a RIFF/WAVE file at `target_sr` (librosa.load(path, sr=target_sr) for the
+    reference's preprocessed clips; see the module docstring)."""
+    x, sr = read_wav(path)
+    nch = x.shape[1]
     x = x.mean(axis=1, dtype=np.float32) if nch > 1 else x[:, 0]   # librosa.to_mono: channel mean
     if sr != target_sr:
         from math import gcd
@@ -81,6 +93,86 @@ def load_wav_16k(path: str, target_sr: int = TARGET_SR) -> np.ndarray:
         g = gcd(sr, target_sr)
         x = resample_poly(x, target_sr // g, sr // g).astype(np.float32)
     return np.ascontiguousarray(x, dtype=np.float32)
+
+
+MIN_OUT_SAMPLES = 400      # the WavLM conv stack's receptive field: a shorter clip has no frame at all
+
+
+def _clip(path: str, max_seconds, min_samples: int):
+    """One file of a batch: (samples [n, nch] cut to max_seconds, rate, filter table, n_out, whether it was cut), or a
+    ValueError naming the file."""
+    from fddm_hip import audio, ops
+    x, sr = read_wav(path)
+    keep = x.shape[0] if max_seconds is None else min(x.shape[0], int(max_seconds * sr))
+    was_cut = x.shape[0] > keep
+    x = x[:keep]
+    n, nch = x.shape
+    if not 1 <= nch <= ops.WAV_MAX_CHANNELS:
+        raise ValueError(f"{path}: {nch} channels (1 .. {ops.WAV_MAX_CHANNELS} are supported)")
+    try:
+        t = audio.sinc_resample_taps(sr)
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
+    n_out = -((-n * t.P) // t.Q)
+    if n_out < min_samples:
+        raise ValueError(f"{path}: {n} frames at {sr} Hz give {n_out} samples at {TARGET_SR} Hz, fewer than the "
+                         f"{min_samples} the encoder needs for one frame")
+    return x, sr, t, n_out, was_cut
+
+
+def check_clip(path: str, max_seconds=20.0, min_samples: int = MIN_OUT_SAMPLES) -> None:
+    """Raises what load_batch would raise for this file alone (host only)."""
+    _clip(str(path), max_seconds, min_samples)
+
+
+def load_batch(paths, device, max_seconds=20.0, pad_to=None, min_samples: int = MIN_OUT_SAMPLES):
+    """WAV files of any rates and channel counts -> (wave [B, T] f32, lengths [B] int64, info) on `device`: the
+    inference front end (reference inference.py:53-61 per file — channel mean, torchaudio's sinc resampler to 16 kHz —
+    here for a padded batch and on the GPU, fddm_hip.ops.wav_resample).
+
+    Each file is read on the host and cut to `max_seconds` of source frames (20 s is the dataset's cap; None: no cut);
+    the raw interleaved samples of the whole batch are packed into one buffer and copied to the device once; one launch
+    per distinct source rate writes the rows. T is the longest output in the batch, or `pad_to`; samples past a row's
+    length are zeros. info: sample_rates, channels, frames (after the cut), truncated (cut by max_seconds or by pad_to),
+    launches. A clip with fewer than `min_samples` = 400 output samples raises a ValueError naming the file: the
+    encoder would give it no frame, and the decoder a fully masked (NaN) entry."""
+    from fddm_hip import audio, ops
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"load_batch: device {device}: the audio front end is a GPU kernel, there is no CPU fallback")
+    if device.index is not None and device.index != torch.cuda.current_device():
+        raise ValueError(f"load_batch: device {device} is not the current device (cuda:{torch.cuda.current_device()}); "
+                         "the kernels launch on the current device: torch.cuda.set_device / torch.cuda.device first")
+    paths = [str(p) for p in paths]
+    if not paths:
+        raise ValueError("load_batch: no files")
+    clips, desc, n_outs, cut = [], [], [], []
+    off = 0
+    for row, path in enumerate(paths):
+        x, sr, _, n_out, was_cut = _clip(path, max_seconds, min_samples)
+        n, nch = x.shape
+        cut.append(was_cut)
+        clips.append((off, x.reshape(-1)))
+        desc.append((sr, (off, n, nch, row)))
+        n_outs.append(n_out)
+        off += (n * nch + 3) // 4 * 4       # clips start on 16-byte boundaries (the kernel's wide loads)
+    T = int(pad_to) if pad_to is not None else max(n_outs)
+    if T < 1:
+        raise ValueError(f"load_batch: pad_to = {pad_to}")
+    packed = np.zeros(off, dtype=np.float32)
+    for o, flat in clips:
+        packed[o:o + flat.size] = flat
+    src = torch.from_numpy(packed).to(device)
+    wave = torch.empty(len(paths), T, device=device, dtype=torch.float32)
+    lengths = torch.empty(len(paths), device=device, dtype=torch.int64)
+    rates = sorted({sr for sr, _ in desc})
+    for sr in rates:
+        t, taps, klo = audio.device_taps(sr, device)
+        ops.wav_resample(src, [d for r, d in desc if r == sr], taps, klo, t.P, t.Q, t.W, wave, lengths)
+    info = {"sample_rates": [sr for sr, _ in desc], "channels": [d[2] for _, d in desc],
+            "frames": [d[1] for _, d in desc], "truncated": [c or n > T for c, n in zip(cut, n_outs)],
+            "launches": len(rates)}
+    return wave, lengths, info
 
 
 def _nmt_nfkc_normalizer():

@@ -1260,3 +1260,62 @@ def jump(logits2d, xt, coef, L, mode=0, temperature=1.0, seed=0, rng_stream=0, x
     call("fddm_jump", ptr(logits2d), logits2d.stride(0), ptr(xt), ptr(coef), ptr(x_next), ptr(x0hat), N, L, V, mode,
          float(temperature), seed, rng_stream, stream())
     return x_next, x0hat
+
+
+# ------------------------------------------------------------------------------------ audio front end
+WAV_MAX_CHANNELS = 8
+
+
+def wav_resample(src, desc, taps, klo, P, Q, W, wave, lengths):
+    """Clips of raw interleaved f32 samples at one source rate -> 16 kHz mono rows of a padded batch, one launch
+    (csrc/audio.hip; the contract is at fddm_wav_resample in include/fddm_hip.h).
+    src f32 1-D on the GPU; desc: one (first float in src, frames, channels, destination row) per clip, host integers;
+    taps f32 [NT, P] and klo int32 [P]: the compacted table of fddm_hip.audio.device_taps; wave f32 [rows, T]
+    contiguous, lengths int64 [rows]. Writes wave[row] and lengths[row] of every named row; returns (wave, lengths)."""
+    import ctypes
+
+    from . import audio as _audio
+    dev = wave.device
+    P, Q, W = int(P), int(Q), int(W)
+    _chk(P >= 1 and Q >= 1 and W >= 0, "wav_resample: P, Q >= 1 and W >= 0")
+    KT = 2 * W + Q
+    # messages are built only on failure: this is the launch path
+    if not (taps.dim() == 2 and taps.shape[1] == P and 1 <= taps.shape[0] <= KT and taps.dtype == torch.float32
+            and taps.is_contiguous()):
+        raise ValueError(f"wav_resample: taps is a contiguous f32 [NT <= {KT}, P = {P}] table, got "
+                         f"{tuple(taps.shape)} {taps.dtype}")
+    if not (klo.dtype == torch.int32 and tuple(klo.shape) == (P,) and klo.is_contiguous()):
+        raise ValueError(f"wav_resample: klo is a contiguous int32 [{P}] vector")
+    if _audio.lds_span_bytes(P, Q, KT) > _audio.LDS_MAX_BYTES:
+        raise ValueError(f"wav_resample: the input span of P = {P}, Q = {Q}, W = {W} exceeds the kernel's LDS")
+    _chk(wave.dim() == 2 and wave.dtype == torch.float32 and wave.is_contiguous() and wave.shape[1] >= 1,
+         "wav_resample: wave is a contiguous f32 [rows, T >= 1] tensor")
+    rows, T = wave.shape
+    _chk(T <= 2 ** 31 - 1 - _audio.OUT_BLOCK, "wav_resample: T below 2^31 - 1024")
+    _chk(lengths.dtype == torch.int64 and tuple(lengths.shape) == (rows,) and lengths.is_contiguous(),
+         "wav_resample: lengths is a contiguous int64 [rows] vector")
+    _chk(src.dim() == 1 and src.dtype == torch.float32 and src.is_contiguous(), "wav_resample: src is a contiguous f32 vector")
+    _chk(wave.is_cuda and all(t.device == dev for t in (src, taps, klo, lengths)), "wav_resample: every tensor on one GPU")
+    # the launch goes to the current device's current stream (stream()): tensors of another GPU would be read and written
+    # by a kernel running on the wrong device
+    if dev.index != _cur_device():
+        raise ValueError(f"wav_resample: the tensors are on {dev} but the current device is cuda:{_cur_device()} "
+                         "(torch.cuda.set_device / torch.cuda.device first)")
+    nsrc = src.numel()
+    seen = set()
+    flat = []
+    for d in desc:
+        off, n, nch, row = (int(v) for v in d)
+        if not 1 <= nch <= WAV_MAX_CHANNELS:
+            raise ValueError(f"wav_resample: {nch} channels (1 .. {WAV_MAX_CHANNELS})")
+        if not (0 <= off <= nsrc and n >= 0 and off + n * nch <= nsrc and n * P < 2 ** 31):
+            raise ValueError(f"wav_resample: clip (offset {off}, {n} frames, {nch} channels) outside src ({nsrc} floats)")
+        if not 0 <= row < rows or row in seen:
+            raise ValueError(f"wav_resample: destination row {row} (distinct rows of {rows})")
+        seen.add(row)
+        flat += (off, n, nch, row)
+    if not flat:
+        return wave, lengths
+    call("fddm_wav_resample", ptr(src), nsrc, (ctypes.c_long * len(flat))(*flat), len(flat) // 4, ptr(taps), ptr(klo),
+         int(taps.shape[0]), P, Q, W, ptr(wave), ptr(lengths), rows, T, stream())
+    return wave, lengths

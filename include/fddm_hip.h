@@ -412,6 +412,30 @@ int fddm_jump(const float* logits, long ldz, const long* xt, const float* coef, 
               long L, long V, int mode, float temperature, unsigned long long seed, unsigned long long stream,
               void* hip_stream);
 
+/* ---- audio front end of inference.py (reference inference.py:53-61: torchaudio.load, channel mean,
+ *      torchaudio.functional.resample(wav, sr, 16000) — Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99):
+ *      one launch per source rate turns B clips of raw interleaved f32 samples into 16 kHz mono rows of a padded batch.
+ *      Table (fddm_hip/audio.py sinc_resample_taps, float64 rounded once to f32): g = gcd(rate, 16000), Q = rate / g,
+ *      P = 16000 / g, base = min(Q, P) * rolloff, W = ceil(width * Q / base), KT = 2 W + Q taps per phase,
+ *        t = clamp((-p / P + (k - W) / Q) * base, -width, width),
+ *        h[p][k] = sinc(pi t) cos^2(pi t / (2 width)) base / Q.
+ *      The kernel takes it compacted: entries below 1e-20 are zeros, klo[p] (int [P]) is where phase p's nonzero
+ *      span starts and taps [NT][P] holds taps[i][p] = h[p][klo[p] + i], NT the longest span (klo[p] + NT <= KT).
+ *      desc is a HOST array of 4 longs per clip: {first float in src, frames n, channels nch, destination row}.
+ *        xm[i] = (src[i nch] + ... + src[i nch + nch - 1]) / nch   (f32, channel order, true division; 0 outside [0, n))
+ *        n_out = min(T, ceil(n P / Q))
+ *        wave[row][j] = sum_k h[j % P][k] xm[(j / P) Q + k - W]    (f32, k ascending from 0) for j < n_out,
+ *        wave[row][j] = 0 for n_out <= j < T,  lengths[row] = n_out.
+ *      n = 0 gives a zero row and length 0; rows no clip names are not touched. 16 kHz input (P = Q = 1, W = 0, one
+ *      tap 1.0f) comes out bit for bit. wave [rows][T] f32 contiguous, lengths [rows] int64. hipErrorInvalidValue,
+ *      before any launch, when: P, Q < 1, W < 0, NT outside 1 .. 2 W + Q, T < 1, the mono span of 1024 outputs
+ *      (((1023 / P) + 1) Q + KT frames) exceeds 64 KiB of LDS, or a descriptor has nch outside 1 .. 8, a row outside
+ *      [0, rows), a row another descriptor names, an offset outside [0, src_len] or samples outside [0, src_len).
+ *      The launch goes to the current device: every pointer must belong to it. 16-byte loads need src 16-byte aligned and clip offsets that are
+ *      multiples of 4 floats (mono and stereo); anything else takes the scalar path. */
+int fddm_wav_resample(const float* src, long src_len, const long* desc, long B, const float* taps, const int* klo,
+                      int NT, int P, int Q, int W, float* wave, long* lengths, long rows, long T, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
